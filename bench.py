@@ -20,9 +20,17 @@ roofline   = the dominant (only) kernel's algorithmic bytes / its average launch
 cpu_baseline = the C restatement of checksum.go (oracle/, "port", reference-faithful
              -O2 -fno-tree-vectorize) on host cores over a bounded sample of the
              same batch (rank 0, N=1 only); the same leg checks the GPU results
-             of the timed batch bit-for-bit against it.
+             of the timed batch bit-for-bit against it. (--full only)
 
-Run: python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--launch-check]
+A plain run sets up the one workload, warms up, times --steps launches and prints the
+line. --full adds every other measurement and check: the side configs
+(other_configs), the host-memory end-to-end figures, the CPU baseline with its
+full-batch parity check, and the in-place writer's self-check (Workload.check_fill);
+--no-extra / --no-e2e / --no-cpu-baseline drop single legs of a --full run.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
+
+Run: python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--full]
+                     [--dump-outputs DIR] [--launch-check]
 """
 from __future__ import annotations
 
@@ -53,9 +61,10 @@ def log(*a):
 
 
 class Workload:
-    """One BASELINE config, materialised on the device with R rotating copies."""
+    """One BASELINE config, materialised on the device with R rotating copies.
+    check=False leaves out the in-place writer's self-check (a plain bench run)."""
 
-    def __init__(self, cfg: int, dev: torch.device, seed: int):
+    def __init__(self, cfg: int, dev: torch.device, seed: int, check: bool = True):
         self.cfg = cfg
         self.dev = dev
         g = torch.Generator(device=dev)
@@ -155,7 +164,7 @@ class Workload:
         if self.offsets is not None:  # validate once; the timed launches skip the check
             batch.checksum_ragged(self.data[0], self.offsets, self.mode,
                                   initial_arr=self.initial_arr, addrs=self.addrs, out=self.out)
-        if self.fill:
+        if self.fill and check:
             self.check_fill()
         # algorithmic bytes per launch: payload + side arrays + uint16 out
         self.bytes = self.payload + self.side + 2 * n * batch.outputs(self.mode)
@@ -214,6 +223,15 @@ class Workload:
         if not (torch.equal(got.to(torch.int32), want) and torch.equal(self.stored_fields(d), want)):
             raise SystemExit(f"config {self.cfg}: the in-place writer disagrees with the read-only kernel")
         del d
+
+    def outputs(self, k: int) -> dict:
+        """What a caller of the timed path holds after step k, as float32 arrays (uint16
+        values are exact in float32): the result array the step filled, or, for the
+        in-place writers, the checksum fields it stored into that step's batch, in
+        result order (stored_fields). At most 8 MB (2 results x 1M packets x 4 B)."""
+        if self.fill:
+            return {"stored_fields": self.stored_fields(self.data[k % self.R]).cpu().numpy().astype(np.float32)}
+        return {"checksums": self.out.cpu().numpy().astype(np.float32)}
 
     def kernel_name(self) -> str:
         if self.offsets is not None:
@@ -831,16 +849,25 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", type=int, default=3, choices=SIDE_CONFIGS)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the side-config measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the side configs, the host-memory end-to-end path and the CPU "
+                         "baseline, and check the timed batch against the oracle (a plain run times "
+                         "--config only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the side-config measurements")
     ap.add_argument("--cpu-budget", type=float, default=6.0, help="wall seconds for the CPU baseline")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the host-memory end-to-end measurement")
+    ap.add_argument("--no-e2e", action="store_true",
+                    help="with --full: skip the host-memory end-to-end measurement")
     ap.add_argument("--launch-check", action="store_true",
                     help="start the ranks, rendezvous, print their placement; no GPU work")
     ap.add_argument("--host-multi", metavar="DEVS", default=None,
                     help="(child of the bench) host memory over the listed GPUs, e.g. 0,1,2,3; "
                          "prints one JSON object")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit(f"--steps must be >= 1 and --warmup >= 0 (got {args.steps}, {args.warmup})")
 
     if args.host_multi is not None:
         _imports()
@@ -874,8 +901,12 @@ def rank_main(args, plan: dict) -> None:
         else:
             torch.distributed.init_process_group("gloo")
 
-    w = Workload(args.config, dev, seed=1000 + rank)
+    w = Workload(args.config, dev, seed=1000 + rank, check=args.full)
     wall, kern = timed(w, args.steps, args.warmup, dist)
+    if args.dump_outputs:  # before any --full leg launches the path again
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in w.outputs(args.warmup + args.steps - 1).items():
+            np.save(os.path.join(args.dump_outputs, name + (f"_rank{rank}" if dist else "") + ".npy"), arr)
     # the only collective: each rank's (wall, kernel time, bytes), for the slowest
     # rank's wall time and the per-GPU figures
     per = gather_over_ranks([wall, kern, float(w.bytes), float(plan["device"])],
@@ -933,7 +964,7 @@ def rank_main(args, plan: dict) -> None:
         },
     }
 
-    if rank == 0 and world == 1 and not args.no_extra:
+    if args.full and rank == 0 and world == 1 and not args.no_extra:
         extra = {}
         for c in SIDE_CONFIGS:
             if c == args.config:
@@ -956,10 +987,10 @@ def rank_main(args, plan: dict) -> None:
             torch.cuda.empty_cache()
         res["other_configs"] = extra
 
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if args.full and rank == 0 and world == 1 and not args.no_e2e:
         res["end_to_end_host_memory"] = end_to_end(w)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         parity, cb = cpu_baseline(w, host_threads(), args.cpu_budget)
         res["cpu_baseline"] = cb
         res["parity_full_batch_vs_oracle"] = parity
@@ -969,7 +1000,7 @@ def rank_main(args, plan: dict) -> None:
     if dist:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
-    if rank == 0 and dist and not args.no_e2e and plan["ndev"] >= world:
+    if args.full and rank == 0 and dist and not args.no_e2e and plan["ndev"] >= world:
         # Host memory over all the job's GPUs at once (rank 0). Taken after the group
         # is torn down: a rank waiting in an RCCL barrier meanwhile would keep a
         # collective kernel spinning on its GPU. The other ranks have left the timed

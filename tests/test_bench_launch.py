@@ -146,8 +146,10 @@ def test_mismatch_exits_nonzero():
 
 
 def test_failing_rank_fails_the_launch():
-    # no GPU here: every rank fails at its device; the launcher must not report success
-    r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--no-extra", "--no-e2e", "--no-cpu-baseline"])
+    # no GPU for the ranks (hidden from them where the box has one): every rank fails at
+    # its device; the launcher must not report success
+    r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--no-extra", "--no-e2e", "--no-cpu-baseline"],
+             env={"HIP_VISIBLE_DEVICES": ""})
     assert r.returncode != 0
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
 
@@ -214,10 +216,11 @@ def test_rank_ignoring_sigterm_is_killed_after_grace():
     assert not any(_alive(x) for x in pids)
 
 
-def test_host_multi_child_failure_is_reported_not_fatal():
+def test_host_multi_child_failure_is_reported_not_fatal(monkeypatch):
     """The multi-GPU host measurement runs in a child (`--host-multi`): a child that
-    cannot run (here: no GPU) or outlives its limit leaves an error entry, and the
-    caller — the bench line — carries on."""
+    cannot run (here: no GPU, hidden from the child where the box has one) or outlives
+    its limit leaves an error entry, and the caller — the bench line — carries on."""
+    monkeypatch.setenv("HIP_VISIBLE_DEVICES", "")
     r = bench.host_multi_isolated(3, [0, 1], timeout=300)
     assert list(r) == ["pinned_2gpu_error"] and "child exited" in r["pinned_2gpu_error"], r
     r = bench.host_multi_isolated(3, [0, 1], timeout=0.05)

@@ -147,7 +147,7 @@ def test_bench_fill_configs_check_against_oracle(dev, config):
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "YU_BENCH_BACKEND")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", str(config), "--steps", "5",
-                        "--warmup", "2", "--no-extra", "--no-e2e", "--cpu-budget", "1"],
+                        "--warmup", "2", "--full", "--no-extra", "--no-e2e", "--cpu-budget", "1"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -155,6 +155,44 @@ def test_bench_fill_configs_check_against_oracle(dev, config):
     line = json.loads(lines[0])
     assert line["parity_full_batch_vs_oracle"] is True, line
     assert line["cpu_baseline"]["value"] > 0
+
+
+@pytest.mark.parametrize("config,name", [(3, "checksums"), (13, "stored_fields")])
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(dev, tmp_path, monkeypatch, config, name):
+    """A plain run times --steps launches of --config and nothing else (no side configs,
+    host-memory leg, CPU baseline or parity leg in the line), and --dump-outputs writes
+    what the last timed step computed: the result array (config 3), or the fields the
+    in-place writer stored into that step's batch (config 13), as float32. The same
+    seeded workload replayed here, launch for launch, gives the same values."""
+    import torch
+    import bench
+    steps, warmup = 3, 2
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "YU_BENCH_BACKEND")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", str(config),
+                        "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path / "dump")],
+                       env=env, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == steps and line["warmup"] == warmup and line["ms_per_step"] > 0
+    assert line["value"] > 0 and line["unit"] == "GiB/s" and line["higher_is_better"] is True
+    assert line["cpu_baseline"] is None
+    assert not {"other_configs", "end_to_end_host_memory", "parity_full_batch_vs_oracle"} & set(line)
+    assert sorted(os.listdir(tmp_path / "dump")) == [name + ".npy"]
+    got = np.load(tmp_path / "dump" / (name + ".npy"))
+    assert got.dtype == np.float32 and got.shape == (bench.N_PKT,)
+    from yustack_amd import batch
+    for k, v in (("np", np), ("torch", torch), ("batch", batch)):  # what bench._imports() binds, undone after
+        monkeypatch.setattr(bench, k, v)
+    w = bench.Workload(config, dev, seed=1000, check=False)
+    for k in range(warmup + steps):
+        w.step(k)
+    torch.cuda.synchronize()
+    want = w.outputs(warmup + steps - 1)[name]
+    assert np.array_equal(got, want)
+    assert len(np.unique(got)) > 1000  # real checksums, not a cleared buffer
 
 
 def _bench_line(n, timeout):
