@@ -200,7 +200,7 @@ def test_variant_selection_by_batch_size(stride, length, n, want):
 
 
 # k_seg's TX / RX / DG kinds keep positions in 32 bits: 63 strides plus a 65535-byte
-# packet and its 3 head bytes must stay under 2 GiB (kSeg32Stride in yucsum_kernels.hip)
+# packet and its 3 head bytes must stay under 2 GiB (kSeg32Stride in yucsum_plan.cpp)
 SEG32_STRIDE = ((1 << 31) - 65535 - 3) // 63
 
 

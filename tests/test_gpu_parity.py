@@ -185,8 +185,8 @@ def _ragged_headers(rng, blob, offs, mode):
 @pytest.mark.parametrize("lo,hi", [(0, 64), (40, 200), (64, 1500)])
 @pytest.mark.parametrize("mode", list(range(8)))
 def test_ragged_small_packets(dev, oracle_c, mode, lo, hi):
-    """tun-style RX bursts: mostly short packets (k_rag's group path) with a
-    few long ones sprinkled in (its whole-wave phase 2), every start alignment."""
+    """tun-style RX bursts: mostly short packets with a few long ones sprinkled
+    in (chunks of one tile next to chunks of many), every start alignment."""
     rng = np.random.default_rng(7000 + 17 * mode + hi)
     mn = {O.MODE_UDP: 8, O.MODE_TCP: 60, O.MODE_VERIFY_TCP: 60, O.MODE_ICMP: 4,
           O.MODE_IPV4: 60, O.MODE_VERIFY_IPV4: 60}.get(mode, 0)
@@ -209,9 +209,8 @@ def test_ragged_small_packets(dev, oracle_c, mode, lo, hi):
 
 @pytest.mark.parametrize("mode", [O.MODE_RAW])
 def test_ragged_far_from_step_base(dev, oracle_c, mode):
-    """A 2.1 GiB packet followed by short ones: the short packets of its step lie
-    more than 1 GiB past the step's first packet, which k_rag's 32-bit lane
-    offsets cannot reach, so they take the whole-wave path; the later steps sit
+    """A 2.1 GiB packet followed by short ones: the short packets start more than
+    2 GiB past the batch's first byte, out of reach of 32-bit offsets from there,
     at offsets with bit 31 set (a sign-extension trap for 32-bit lane reads)."""
     big = (2 << 30) + (100 << 20) + 3
     lens = np.array([big, 64, 65, 20, 100, 7] + [60] * 10, dtype=np.int64)

@@ -11,6 +11,6 @@ mkdir -p tests/cpp/build
   -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-omit-frame-pointer \
   -DYU_TEST_QUICK_EXIT -Iinclude -Iyustack_amd/csrc \
   tests/cpp/test_checksum.cpp yustack_amd/csrc/yucsum_host.cpp yustack_amd/csrc/yucsum_scalar.cpp \
-  yustack_amd/csrc/yucsum_kernels.hip \
+  yustack_amd/csrc/yucsum_kernels.hip yustack_amd/csrc/yucsum_plan.cpp \
   -Loracle/build -lcsum_oracle -Wl,-rpath,'$ORIGIN/../../../oracle/build' \
   -o tests/cpp/build/test_checksum_asan

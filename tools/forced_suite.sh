@@ -7,7 +7,7 @@
 set -o pipefail
 TAG=${1:-forced}
 mkdir -p gpurun_out/forced
-for v in ${FORCED_VARIANTS:-rag seg4 seg16 loop}; do
+for v in ${FORCED_VARIANTS:-seg4 seg16 loop}; do
   # the override took effect: the kernel the library picks for a 1M-packet RAW batch
   echo "$v: picks $(YU_TUNING=1 YU_RAGGED=$v python -c 'from yustack_amd import batch; print(batch.ragged_variant("raw", 1 << 20))' 2>/dev/null)"
   YU_TUNING=1 YU_RAGGED=$v timeout -k 10 600 python -u -m pytest tests/test_gpu_parity.py tests/test_gpu_contract.py \

@@ -110,7 +110,7 @@ int main(int argc, char **argv) {
       // 9: U{40..600}, 10: U{40..1000} (RAW + initial): small-grid crossover
       const int lo = (cfg == 4 || cfg == 5 || cfg == 7) ? 64 : 40;
       const int hi = cfg == 4 ? 9000 : ((cfg == 5 || cfg == 7 || cfg == 11 || cfg == 12 || cfg == 15) ? 1500 : (cfg == 9 ? 600 : (cfg == 10 ? 1000 : 200)));
-      // 11: U{40..1500} IPv4 datagrams, header checksum only (k_rag)
+      // 11: U{40..1500} IPv4 datagrams, header checksum only (k_hdr)
       if (cfg == 11 || cfg == 12) mode = YU_MODE_IPV4;  // 12: IHL 5 in every header
       if (cfg == 7) mode = YU_MODE_TCP;
       if (cfg == 8) mode = YU_MODE_UDP;

@@ -25,7 +25,7 @@ __device__ __forceinline__ uint64_t tstamp(uint32_t dep) {
   return t;
 }''')
 rep('''    const bool last = t * T + T >= cur.xe;  // wave-uniform
-    SegChunk nn;''','''    const bool last = t * T + T >= cur.xe;  // wave-uniform
+''','''    const bool last = t * T + T >= cur.xe;  // wave-uniform
     const bool trw = A.trace && (wave % 61u) == 0u && trk < 64u;
     uint64_t trs[7];
     trs[0] = trw ? tstamp(0u) : 0u;
@@ -41,7 +41,7 @@ rep('''    const bool last = t * T + T >= cur.xe;  // wave-uniform
       }
       ++trk;
     };
-    SegChunk nn;''')
+''')
 rep('''    seg_fetch<U, NT != 0>(last ? nxt.b0 : cur.b0, last ? nxt.xe : cur.xe, last ? 0u : t + 1u, lane,
                           end, cn);
 ''','''    trs[1] = trw ? tstamp((uint32_t)nxt.b0) : 0u;
@@ -50,9 +50,9 @@ rep('''    seg_fetch<U, NT != 0>(last ? nxt.b0 : cur.b0, last ? nxt.xe : cur.xe,
     trs[2] = trw ? tstamp(c[0].x) : 0u;
     trs[3] = trw ? tstamp(c[U - 1].w) : 0u;
 ''')
-rep('''    bool here = false;
+rep('''    bool here = false;  // a packet boundary (or header) lies in this tile
 #pragma unroll''','''    trs[4] = trw ? tstamp(carry_l) : 0u;
-    bool here = false;
+    bool here = false;  // a packet boundary (or header) lies in this tile
 #pragma unroll''')
 rep('''#pragma unroll
     for (int i = 0; i < NP; ++i)
@@ -71,20 +71,20 @@ rep('''    if (!last) {
     }
     // end sums: the next lane's start (ragged), else this lane's end point''')
 rep('''    if ((ch + nwave) * CH >= A.n) return true;
-    cur = nxt;''','''    trec(1u, pt[NP - 1].p ^ (uint32_t)cur.oy);
+    cur = nxt;''','''    trec(1u, pt[NP - 1].p ^ (uint32_t)cur.xe);
     if ((ch + nwave) * CH >= A.n) return true;
     cur = nxt;''')
 rep('''  uint64_t t = 0;
   // One tile: issue the loads of the next item into cn, then sum c.''','''  uint64_t t = 0;
   uint32_t trk = 0;
   // One tile: issue the loads of the next item into cn, then sum c.''')
-rep('''  a.small_waves = (uint32_t)cu_count(dev) * 4u * (uint32_t)seg_small_blocks();
-''','''  a.small_waves = (uint32_t)cu_count(dev) * 4u * (uint32_t)seg_small_blocks();
+rep('''  a.small_waves = p.small_waves;
+''','''  a.small_waves = p.small_waves;
   a.trace = g_debug_trace;
 ''')
-rep('''int launch(const Variant &v, const BatchArgs &A, hipStream_t stream) {''','''uint64_t *g_debug_trace = nullptr;
+rep('''int launch(const yu::Shape &s, const BatchArgs &A, hipStream_t stream) {''','''uint64_t *g_debug_trace = nullptr;
 
-int launch(const Variant &v, const BatchArgs &A, hipStream_t stream) {''')
+int launch(const yu::Shape &s, const BatchArgs &A, hipStream_t stream) {''')
 rep('''extern "C" {
 
 int yu_csum_batch_uniform(''','''extern "C" {

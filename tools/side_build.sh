@@ -15,7 +15,8 @@ mkdir -p "$D/yustack_amd/csrc" "$D/include"
 get() {  # get <repo path> <dest>
   if [ "$REV" = WORK ]; then cp "$ROOT/$1" "$2"; else git -C "$ROOT" show "$REV:$1" > "$2"; fi
 }
-for f in Makefile yucsum_kernels.hip yucsum_host.cpp yucsum_scalar.cpp yucsum_internal.h; do
+for f in Makefile yucsum_kernels.hip yucsum_plan.cpp yucsum_plan.h yucsum_host.cpp yucsum_scalar.cpp \
+         yucsum_internal.h; do
   get "yustack_amd/csrc/$f" "$D/yustack_amd/csrc/$f"
 done
 get include/yucsum.h "$D/include/yucsum.h"

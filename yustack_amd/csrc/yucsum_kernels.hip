@@ -45,8 +45,8 @@
 // loads in flight while the current step is summed (software pipelining).
 //
 // Work mapping (wave64-first, not a warp tiling). Which kernel a batch gets
-// depends on its layout, mode, packet size and count (pick_uniform /
-// pick_ragged below, each cut-over measured):
+// depends on its layout, mode, packet size and count (yu::plan in
+// yucsum_plan.cpp, each cut-over measured):
 //   k_lane<U>: dense uniform 4-aligned packets up to 112 bytes (configs 2 and
 //     8): 64 whole strides per wave step parked in LDS, one lane per packet
 //     summing it from there.
@@ -68,27 +68,25 @@
 //     and ragged: one lane per packet, 32-byte reads.
 //   k_loop<U, BE> / k_loop_rx<U>: one wave per packet, for ragged bursts of up
 //     to 4096 packets and for few or sparse uniform packets > 4 KiB.
-//   k_rag<G, U>: the first ragged kernel, kept as a measurement alternative.
 //   All are grid-stride kernels; the grid is sized per CU and over-subscribed
-//   (see blocks_per_cu), except that k_seg narrows it for small packets
-//   (seg_waves).
+//   (see blocks_per_cu in yucsum_plan.cpp), except that k_seg narrows it for
+//   small packets (seg_waves).
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include <atomic>
 #include <type_traits>
 
 #include "yucsum.h"
 #include "yucsum_internal.h"
+#include "yucsum_plan.h"
 
 namespace {
 
 constexpr uint32_t kSelSwap = 0x02030001u;  // bytes [1,0,3,2]: BE 16-bit halves
 constexpr uint32_t kSelIdent = 0x03020100u; // bytes [0,1,2,3]
-constexpr uint32_t kLEMax = 131072u;        // longest packet the LE sum covers
+using yu::kLEMax;
 
 struct BatchArgs {
   const uint8_t *data;
@@ -222,8 +220,14 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t v, uint32_t l) {
          (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
 }
 
+__device__ __forceinline__ uint64_t shfl64(uint64_t v, uint32_t src) {
+  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, (int)src, 64);
+  const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), (int)src, 64);
+  return ((uint64_t)hi << 32) | lo;
+}
+
 // Out-of-range offset: the load returns zeros and touches no memory.
-constexpr uint32_t kOOB = 0x80000000u;
+using yu::kOOB;
 
 // Descriptor over [base, min(ceil4(end), base + 2 GiB)). The range check is
 // per dword (a dword reaching past num_records reads as 0), so the extent is
@@ -1072,7 +1076,7 @@ __global__ __launch_bounds__(256) void k_loop(BatchArgs A) {
 // ragged batches, one lane per packet. Only b[:HeaderLength()] (<= 60 bytes)
 // of each packet is summed (header/ipv4.go:177-179, checker/checker.go:32),
 // so streaming every byte (k_seg) or giving each packet a 16-lane group
-// (k_rag: 4 packets per wave step) does far more work than needed. Here a
+// (4 packets per wave step) does far more work than needed. Here a
 // wave step covers 64 packets: each lane loads the 64-byte window at
 // floor4(start) (four dwordx4, cut at the packet's end), reads IHL from its
 // first dword and sums the header bytes under byte masks.
@@ -1158,219 +1162,6 @@ __global__ __launch_bounds__(256) void k_hdr(BatchArgs A) {
       sd.a = sd.b = 0u;
       sd.i = 0;
       finish_packet(A, p, v, len, sd, step_ok ? fill_at(A, ext, s, len) : nullptr, E - sh);
-    }
-  }
-}
-
-// k_rag<G, U, NT>: ragged batches of small packets (tun-style RX bursts,
-// link/tundev/tundev.go:78-151). One packet per wave iteration (k_loop) is
-// latency-bound when packets are a few hundred bytes; here a wave step holds
-// 64/G packets, one per G-lane group, as in k_small, and a 3-stage pipeline
-// keeps the next steps in flight: the offsets of step t+2 and the packet
-// windows of step t+1 are loaded while step t is summed (phase 1). Packets
-// longer than the 16*G*U-byte group window are skipped there and summed in
-// phase 2, after the step loop: each wave scans 64 offsets at a time, ballots
-// the long packets and sums each with all 64 lanes in 4 KiB windows. The two
-// phases do not overlap, so the kernel pays the larger register budget, not
-// the sum.
-// ---------------------------------------------------------------------
-template <int U>
-struct RagItem {
-  uint4 c[U];
-  Side sd;         // side data of the group's packet
-  uint64_t o;      // this lane's offset: offsets[min(pb + lane % (GPW+1), n)]
-  uint32_t len, sh, eload;
-  bool fits;       // this group's packet is summed in phase 1
-};
-
-__device__ __forceinline__ uint64_t shfl64(uint64_t v, uint32_t src) {
-  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, (int)src, 64);
-  const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), (int)src, 64);
-  return ((uint64_t)hi << 32) | lo;
-}
-
-// Phase 1 takes a packet iff it fits the group window and its window lies
-// within 1 GiB of the step's base (the first packet of its step): lane window
-// offsets are 32-bit. Phase 2 applies the same test and takes the rest.
-__device__ __forceinline__ bool rag_fits(uint32_t need, uint64_t len, uint64_t from_base,
-                                         uint32_t W) {
-  return len <= 0xFFFFFFu && need <= W && from_base < (1ull << 30);
-}
-
-template <int G>
-__device__ __forceinline__ uint64_t rag_offs(const BatchArgs &A, uint64_t pb, uint32_t lane) {
-  constexpr uint32_t GPW = 64u / G;
-  uint64_t i = pb + lane % (GPW + 1u);
-  return A.offsets[i < A.n ? i : A.n];  // unconditional (clamped) load
-}
-
-template <int G, int U, int NT>
-__device__ __forceinline__ void rag_fetch(const BatchArgs &A, const SidePtrs &sp, uint64_t pb,
-                                          uint64_t o, uint32_t gw, uint32_t gl, bool ipv4,
-                                          RagItem<U> &it) {
-  constexpr uint32_t W = 16u * G * U;
-  const uint64_t data = (uint64_t)(uintptr_t)A.data;
-  const uint64_t p = pb + gw;
-  const bool active = p < A.n;
-  const uint64_t so = shfl64(o, gw);
-  const uint64_t eo = shfl64(o, gw + 1u);
-  it.o = o;
-  it.len = active ? (uint32_t)(eo - so) : 0u;
-  const uint64_t sabs = data + so;
-  it.sh = (uint32_t)(sabs & 3u);
-  const uint32_t need = it.sh + (ipv4 ? (it.len < 60u ? it.len : 60u) : it.len);
-  // readfirstlane returns int: widen through uint32_t, never sign-extend
-  const uint64_t o0 = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(o >> 32)) << 32) |
-                      (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)o);
-  const uint64_t base = uniform64((data + o0) & ~3ull);
-  it.fits = active && rag_fits(need, eo - so, (sabs & ~3ull) - base, W);
-  it.eload = it.fits ? need : 0u;
-  const uint32_t lw = it.fits ? (uint32_t)((sabs & ~3ull) - base) : 0u;
-  const __amdgpu_buffer_rsrc_t r = rsrc_at(base, data + A.offsets[A.n]);
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const uint32_t cr = 16u * (gl + (uint32_t)u * G);
-    it.c[u] = bld16(r, cr < it.eload ? lw + cr : kOOB, nt_step<NT>(u, U));
-  }
-  it.sd = load_side(sp, active ? p : A.n - 1);
-}
-
-// One packet summed by the whole wave in 4 KiB windows, no prefetch: the
-// fallback for steps holding a packet longer than the group window.
-template <bool BE>
-__device__ __forceinline__ uint32_t rag_serial_sum(uint64_t sabs, uint32_t len, uint32_t E,
-                                                   uint32_t lane, uint64_t end,
-                                                   uint32_t (&jx)[3], const Junk &j) {
-  constexpr uint32_t W = 64u * 16u * 4u;
-  const uint32_t sh = (uint32_t)(sabs & 3u);
-  const uint32_t sel = (sh & 1u) ? kSelIdent : kSelSwap;
-  uint32_t acc = 0;
-  for (uint32_t wb = 0; wb < sh + len; wb += W) {
-    const __amdgpu_buffer_rsrc_t r = rsrc_at(uniform64((sabs & ~3ull) + wb), end);
-    const uint32_t lim = sh + len - wb;
-    uint4 c[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const uint32_t cr = 16u * (lane + 64u * (uint32_t)u);
-      c[u] = bld16(r, cr < lim ? cr : kOOB, true);
-    }
-    if (wb == 0) junk_take<6>(c[0], 0u, j, jx);
-    if (wb + W <= E) {  // full window (wave-uniform)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) acc = sum_full<BE>(c[u], sel, acc);
-    } else {  // last window: E - wb < W, so the int limits cannot overflow
-      const int f = (int)((E & ~3u) - wb);
-      const int limj[4] = {f, f - 4, f - 8, f - 12};
-      const uint32_t tm = (1u << (8u * (E & 3u))) - 1u;
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        acc = sum_masked<BE>(c[u], 16 * (int)(lane + 64u * (uint32_t)u), limj, tm, sel, acc);
-    }
-  }
-  acc = group_total<64>(acc);
-  const uint32_t s = acc - junk_sum<BE>(jx, j, sel);
-  return BE ? s : le_to_be(s, sh & 1u);
-}
-
-template <int G, int U, int NT>
-__global__ __launch_bounds__(256) void k_rag(BatchArgs A) {
-  constexpr uint32_t GPW = 64u / G;
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t gl = lane & (G - 1);
-  const uint32_t gw = lane / G;
-  const uint64_t wave = grid_wave(A.xcd);
-  const uint64_t step = (uint64_t)gridDim.x * (blockDim.x >> 6) * GPW;
-  const int mode = A.mode;
-  const bool ipv4 = mode_is_ipv4(mode);
-  const SidePtrs sp = side_ptrs(A);
-  const uint64_t data = (uint64_t)(uintptr_t)A.data;
-  const uint64_t end = data + A.offsets[A.n];
-  const Extent ext = batch_extent(A);
-
-  uint64_t pb = wave * GPW;
-  if (pb >= A.n) return;
-  uint64_t o1 = rag_offs<G>(A, pb + step, lane);
-  RagItem<U> it;
-  rag_fetch<G, U, NT>(A, sp, pb, rag_offs<G>(A, pb, lane), gw, gl, ipv4, it);
-  for (;;) {
-    const uint64_t pn = pb + step;
-    const bool more = pn < A.n;  // wave-uniform
-    const uint64_t o2 = rag_offs<G>(A, pb + 2 * step, lane);
-    RagItem<U> nx;
-    rag_fetch<G, U, NT>(A, sp, more ? pn : A.n, o1, gw, gl, ipv4, nx);
-
-    uint32_t E = it.sh + it.len;
-    if (ipv4) {
-      const uint32_t hl = __shfl(ipv4_hl(it.c[0].x, it.sh), (int)(lane & ~(uint32_t)(G - 1)), 64);
-      E = it.sh + (it.len < hl ? it.len : hl);
-    }
-    const int F = (int)(E & ~3u);
-    const int lim[4] = {F, F - 4, F - 8, F - 12};
-    const uint32_t tm = (1u << (8u * (E & 3u))) - 1u;
-    uint32_t acc = 0;
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int cr = 16 * (int)(gl + (uint32_t)u * G);
-      if (__all((int)(!it.fits || cr + 16 <= F)))  // every chunk whole: skip the cut
-        acc = sum_full<false>(it.c[u], 0u, acc);
-      else
-        acc = sum_masked<false>(it.c[u], cr, lim, tm, 0u, acc);
-    }
-    acc = group_total<G>(acc);
-    const Junk j = make_junk(it.sh, E, mode);
-    uint32_t jx[3];
-    junk_take<__builtin_ctz(G)>(it.c[0], lane & ~(uint32_t)(G - 1), j, jx);
-    const uint64_t so = shfl64(it.o, gw);  // all lanes: a cross-lane read needs active sources
-    if (gl == G - 1 && it.fits) {
-      const uint32_t v = le_to_be(acc - junk_sum<false>(jx, j, 0u), it.sh & 1u);
-      finish_packet(A, pb + gw, v, it.len, it.sd, fill_at(A, ext, so, it.len), E - it.sh);
-    }
-    if (!more) break;
-    it = nx;
-    o1 = o2;
-    pb = pn;
-  }
-
-  // phase 2: the packets phase 1 skipped (longer than the group window, or
-  // farther than 1 GiB from their step's base), one whole-wave sum each
-  const uint64_t nwave = (uint64_t)gridDim.x * (blockDim.x >> 6);
-  constexpr uint32_t W1 = 16u * G * U;
-  for (uint64_t cb = wave * 64u; cb < A.n; cb += nwave * 64u) {
-    const uint64_t i = cb + lane;
-    const uint64_t ic = i < A.n ? i : A.n - 1;
-    const uint64_t so = A.offsets[ic];
-    const uint64_t eo = A.offsets[ic + 1];
-    const uint64_t bo = A.offsets[ic - ic % GPW];  // its step's base packet
-    const uint64_t sabs = data + so;
-    const uint64_t len = eo - so;
-    const uint32_t l32 = len < 0x0FFFFFFFu ? (uint32_t)len : 0x0FFFFFFFu;
-    const uint32_t need = (uint32_t)(sabs & 3u) + (ipv4 ? (l32 < 60u ? l32 : 60u) : l32);
-    const bool skipped =
-        i < A.n && !rag_fits(need, len, (sabs & ~3ull) - ((data + bo) & ~3ull), W1);
-    uint64_t mask = __ballot((int)skipped);
-    while (mask) {  // wave-uniform
-      const uint32_t q = (uint32_t)__builtin_ctzll(mask);
-      mask &= mask - 1u;
-      const uint64_t ps = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(so >> 32), q) << 32) |
-                          (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)so, q);
-      const uint64_t pe = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(eo >> 32), q) << 32) |
-                          (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)eo, q);
-      const uint64_t p = cb + q;
-      const uint32_t plen = pe - ps < YU_MAX_RAW_LEN ? (uint32_t)(pe - ps) : YU_MAX_RAW_LEN;
-      const uint64_t pabs = data + ps;
-      const uint32_t sh = (uint32_t)(pabs & 3u);
-      uint32_t E = sh + plen;
-      if (ipv4) {  // only reached for packets far from their step base
-        const __amdgpu_buffer_rsrc_t r = rsrc_at(uniform64(pabs & ~3ull), end);
-        const uint32_t hl = ipv4_hl(__builtin_amdgcn_raw_buffer_load_b32(r, 0, 0, 0), sh);
-        E = sh + (plen < hl ? plen : hl);
-      }
-      const Junk j = make_junk(sh, E, mode);
-      uint32_t pjx[3];
-      const uint32_t v = plen > kLEMax ? rag_serial_sum<true>(pabs, E - sh, E, lane, end, pjx, j)
-                                       : rag_serial_sum<false>(pabs, E - sh, E, lane, end, pjx, j);
-      const Side sd = load_side(sp, p);
-      if (lane == 63) finish_packet(A, p, v, plen, sd, fill_at(A, ext, ps, plen), E - sh);
     }
   }
 }
@@ -2311,225 +2102,50 @@ __global__ __launch_bounds__(256) void k_loop_rx(BatchArgs A) {
 }
 
 // ---------------------------------------------------------------------
-// Host side: variant selection and launch.
+// Host side: launch. Which kernel, form, load policy and grid a batch gets is
+// yu::plan's decision (yucsum_plan.cpp); here are the functions it names.
 // ---------------------------------------------------------------------
 typedef void (*KernelFn)(BatchArgs);
 
-struct Variant {
-  const char *name;
-  uint32_t window;  // bytes covered per packet step (0 = loop kernel)
-  KernelFn fn[3];   // by load policy (bld16): plain, nt, hybrid
-  uint32_t G;       // lanes per packet
-  uint32_t ppw;     // packets per wave step
-  KernelFn fill = nullptr;  // in-place fill instantiation, if it has its own
-  uint32_t run = 0;  // packets per wave run (k_small), 0 = ppw
-  // k_small without runs (PR = 0), by load policy like fn: the in-place fill,
-  // and batches too small to give every wave of the grid a whole run
-  KernelFn inter[3] = {nullptr, nullptr, nullptr};
+struct KernelFns {
+  KernelFn fn[3];     // by load policy (bld16): plain, nt, hybrid; k_small: with runs
+  KernelFn inter[3];  // k_small without runs (PR = 0), by load policy
+  KernelFn fill;      // the in-place instantiation of a kernel that has its own
 };
 
-// k_small runs of 16 packets per wave (one side-record load and one result
-// store per run): config 3 235-246 -> 235-240 us against the interleaved
-// mapping (PR = 0; equal on some boxes), 64-packet runs 248; 1M x 768 B 131.5
-// -> 122.6, x 3000 B 467.8 -> 450.7; 256K x 768 B 43.8 -> 35.0. The in-place
-// fill keeps the interleaved mapping (config 9: 313 vs 328 us with runs), and
-// so do batches of fewer than 8 runs per CU (see launch).
-// profiles/r02/kbench_ab_k_small_runs.log
-constexpr int kSmallRun = 16;
-#define YU_SMALL(G, U)                                                                     \
-  {"k_small<" #G "," #U ">", 16u * G * U,                                                  \
-   {k_small<G, U, 0, kSmallRun>, k_small<G, U, 1, kSmallRun>, k_small<G, U, 2, kSmallRun>}, \
-   G, 64u / G, nullptr, kSmallRun,                                                         \
-   {k_small<G, U, 0, 0>, k_small<G, U, 1, 0>, k_small<G, U, 2, 0>}}
-#define YU_TINY(G, FILL) \
-  {"k_tiny<" #G ">", 16u * G, {k_tiny<G, 0>, k_tiny<G, 1>, k_tiny<G, 1>}, G, 64u, FILL}
+// One row per entry of YU_KERNELS (yucsum_plan.h), from each family's template
+// arguments. Only k_small has a hybrid policy: elsewhere slot 2 repeats nt, and
+// plain for k_hdr.
+#define YU_FNS_Lane(U) {{k_lane<U, 0>, k_lane<U, 1>, k_lane<U, 1>}, {}, nullptr}
+#define YU_TINY_FILL_true(G) k_tiny<G, 1, true>
+#define YU_TINY_FILL_false(G) nullptr
+#define YU_FNS_Tiny(G, OWN_FILL) \
+  {{k_tiny<G, 0>, k_tiny<G, 1>, k_tiny<G, 1>}, {}, YU_TINY_FILL_##OWN_FILL(G)}
+#define YU_FNS_Small(G, U)                                                                   \
+  {{k_small<G, U, 0, yu::kSmallRun>, k_small<G, U, 1, yu::kSmallRun>,                        \
+    k_small<G, U, 2, yu::kSmallRun>},                                                        \
+   {k_small<G, U, 0, 0>, k_small<G, U, 1, 0>, k_small<G, U, 2, 0>}, nullptr}
+#define YU_LOOP_loop_le(NT) k_loop<4, NT, false>
+#define YU_LOOP_loop_be(NT) k_loop<4, NT, true>
+#define YU_LOOP_loop_rx(NT) k_loop_rx<4, NT>
+#define YU_LOOP_loop_dg(NT) k_loop_rx<4, NT, true>
+#define YU_FNS_Loop(ID) {{YU_LOOP_##ID(0), YU_LOOP_##ID(1), YU_LOOP_##ID(1)}, {}, nullptr}
+#define YU_FNS_Hdr() {{k_hdr<0>, k_hdr<1>, k_hdr<0>}, {}, nullptr}
+#define YU_FNS_Seg(U, KIND, CH)                                                              \
+  {{k_seg<U, 0, kSeg##KIND, CH>, k_seg<U, 1, kSeg##KIND, CH>, k_seg<U, 1, kSeg##KIND, CH>}, \
+   {}, nullptr}
+#define YU_X(id, name, family, window, G, ppw, run, grid, own_fill, fill_plain, tile, kind, \
+             ragged_fill, targs)                                                           \
+  YU_FNS_##family targs,
+const KernelFns kFns[] = {YU_KERNELS(YU_X)};
+#undef YU_X
+static_assert(sizeof(kFns) / sizeof(kFns[0]) == yu::kKernelCount, "one row per kernel");
 
-// k_tiny<8> (113..128 bytes) fills with single field stores: its whole-chunk
-// instantiation would spill scalar registers
-const Variant kTiny[] = {YU_TINY(4, (k_tiny<4, 1, true>)), YU_TINY(8, nullptr)};
-
-// window = the largest stride a wave step's U KiB hold (64 packets)
-#define YU_LANE(U) \
-  {"k_lane<" #U ">", 16u * U, {k_lane<U, 0>, k_lane<U, 1>, k_lane<U, 1>}, 1, 64u}
-const Variant kLane[] = {YU_LANE(2), YU_LANE(3), YU_LANE(4),
-                         YU_LANE(5), YU_LANE(6), YU_LANE(7), YU_LANE(8)};
-
-// Ordered by window; for each window the variant with the most packets per
-// wave comes first (amortises the per-packet epilogue over more bytes).
-const Variant kSmall[] = {
-    YU_SMALL(4, 1),  YU_SMALL(8, 1),  YU_SMALL(8, 2),  YU_SMALL(16, 2),
-    YU_SMALL(16, 3), YU_SMALL(16, 4), YU_SMALL(16, 6), YU_SMALL(32, 4),
-    YU_SMALL(32, 6), YU_SMALL(64, 4),
-};
-const Variant kLoopLE = {"k_loop<4,LE>", 0, {k_loop<4, 0, false>, k_loop<4, 1, false>, k_loop<4, 1, false>}, 64, 1};
-const Variant kLoopBE = {"k_loop<4,BE>", 0, {k_loop<4, 0, true>, k_loop<4, 1, true>, k_loop<4, 1, true>}, 64, 1};
-const Variant kLoopRx = {"k_loop<4,rx>", 0, {k_loop_rx<4, 0>, k_loop_rx<4, 1>, k_loop_rx<4, 1>}, 64, 1};
-const Variant kLoopDg = {"k_loop<4,dg>", 0,
-                         {k_loop_rx<4, 0, true>, k_loop_rx<4, 1, true>, k_loop_rx<4, 1, true>}, 64, 1};
-const Variant kRag = {"k_rag<16,6>", 1536, {k_rag<16, 6, 0>, k_rag<16, 6, 1>, k_rag<16, 6, 2>}, 16, 4};
-// plain loads by default: for scattered 32-byte header reads they beat nt
-// ones (30.7 vs 32.5 us, kbench 12)
-const Variant kHdr = {"k_hdr", 0, {k_hdr<0>, k_hdr<1>, k_hdr<0>}, 64, 64};
-// 64 packets per chunk. (63 packets and a marker lane, kMarker, which drops the
-// end-point slot: small RX datagrams 27.0 -> 26.6 us, but config 4 703 -> 714 and
-// U{64..1500} 127 -> 129 from the 1.6 % more chunks; the 16-packet chunks use it.
-// profiles/r03/kbench_ab_kseg_lean.log)
-#define YU_SEG(U, K, name) \
-  {name, 0, {k_seg<U, 0, K, 64>, k_seg<U, 1, K, 64>, k_seg<U, 1, K, 64>}, 64, 64}
-#define YU_SEG16(U, K, name) \
-  {name, 0, {k_seg<U, 0, K, 16>, k_seg<U, 1, K, 16>, k_seg<U, 1, K, 16>}, 64, 16}
-const Variant kSeg4 = YU_SEG(4, kSegPlain, "k_seg<4>");
-const Variant kSeg8 = YU_SEG(8, kSegPlain, "k_seg<8>");
-const Variant kSegTx4 = YU_SEG(4, kSegTx, "k_seg<4,tx>");
-const Variant kSegTx8 = YU_SEG(8, kSegTx, "k_seg<8,tx>");
-const Variant kSegRx4 = YU_SEG(4, kSegRx, "k_seg<4,rx>");
-const Variant kSegRx8 = YU_SEG(8, kSegRx, "k_seg<8,rx>");
-// 16-packet chunks: 4x the waves for mid-size ragged batches (see pick_ragged)
-const Variant kSeg8c16 = YU_SEG16(8, kSegPlain, "k_seg<8,c16>");
-const Variant kSegTx8c16 = YU_SEG16(8, kSegTx, "k_seg<8,tx,c16>");
-// the TX kinds' in-place form for ragged batches (the whole-line write-back)
-const Variant kSegTxW4 = YU_SEG(4, kSegTxW, "k_seg<4,txw>");
-const Variant kSegTxW8c16 = YU_SEG16(8, kSegTxW, "k_seg<8,txw,c16>");
-const Variant kSegRx8c16 = YU_SEG16(8, kSegRx, "k_seg<8,rx,c16>");
-// (no 4 KiB-tile DG kind: datagram batches take the ragged picks, 8 KiB)
-const Variant kSegDg8 = YU_SEG(8, kSegDg, "k_seg<8,dg>");
-const Variant kSegDg8c16 = YU_SEG16(8, kSegDg, "k_seg<8,dg,c16>");
-// In place, from 64K packets on: smaller chunks. The TXW kind at 48 packets (1M UDP
-// datagrams U{40..200}: 48.7 -> 46.3 us; U{64..1500} TCP 192.9 -> 190.4: a small
-// datagram chunk then fits one 8 KiB tile, so all its fields go out as whole
-// lines), TX_DATAGRAM at 40 (U{40..1500}: 204.3 -> 198.7 us). The read-only kinds
-// keep 64 (RX U{40..200} 26.5 vs 27.5 at 48 and 30.3 at 40; plain unchanged).
-// profiles/r04/kbench_ab_r04v_seg_chunk.log (and r04s/r04t/r04u for 32..60)
-#define YU_SEGC(U, K, CH, name) \
-  {name, 0, {k_seg<U, 0, K, CH>, k_seg<U, 1, K, CH>, k_seg<U, 1, K, CH>}, 64, CH}
-const Variant kSegTxW8c48 = YU_SEGC(8, kSegTxW, 48, "k_seg<8,txw,c48>");
-const Variant kSegDg8c40 = YU_SEGC(8, kSegDg, 40, "k_seg<8,dg,c40>");
-
-// The k_seg kind for a mode (not the IPv4 header-only modes).
-const Variant &seg_for(bool u8, int mode) {
-  if (mode == YU_MODE_VERIFY_RX) return u8 ? kSegRx8 : kSegRx4;
-  if (mode == YU_MODE_TX_DATAGRAM) return kSegDg8;
-  if (mode_is_tx(mode)) return u8 ? kSegTx8 : kSegTx4;
-  return u8 ? kSeg8 : kSeg4;
+KernelFn kernel_fn(const yu::Plan &p) {
+  const KernelFns &f = kFns[p.kernel];
+  if (p.form == yu::Form::Fill) return f.fill;
+  return p.form == yu::Form::Inter ? f.inter[p.policy] : f.fn[p.policy];
 }
-
-// Ragged kernel choice: the segmented stream sum with 8 KiB tiles, except for
-// the IPv4 modes, which read only each packet's header (k_rag's per-packet
-// windows). 8 KiB tiles beat 4 KiB ones from ~800-byte packets up (config 4:
-// 84.9 vs 83.4 % of peak, U{64..1500}: 80.5 vs 77.7 %) and lose below
-// (U{40..200}: 54 vs 61-66 %). Measurement override YU_RAGGED=loop|rag|seg4|seg8.
-// Small bursts (n <= kSmallBurst, e.g. a tun read burst on the host path) go to
-// k_loop instead: k_seg gives each 64-packet chunk to one wave, which streams
-// the chunk's tiles one after another, so a burst of few chunks leaves the GPU
-// idle and pays one memory latency per tile. One wave per packet instead
-// (tools/kbench KB_N, profiles/r01/kbench_ragged_burst_size.log): 64 packets of
-// U{64..1500} 8.6 -> 3.4 us, 1024 of them 10.7 -> 3.8, 2048 jumbo packets
-// U{64..9000} 43.2 -> 5.7; at 4096 small packets U{40..200} the two tie (4.7);
-// from 16384 packets on k_seg wins on small packets (5.4 vs 11.5). VERIFY_RX
-// bursts take k_loop_rx, the same shape.
-constexpr uint64_t kSmallBurst = 4096;
-// the largest uniform stride k_seg's 32-bit kinds take: 63 strides plus a 65535-byte
-// packet and its 3 head bytes stay under 2^31 bytes
-constexpr uint64_t kSeg32Stride = ((1ull << 31) - 65535u - 3u) / 63u;
-constexpr uint64_t kMidBatch = 65536;
-
-const Variant &pick_ragged(int mode, uint64_t n) {
-  static const char *f = yu::tuning_env("YU_RAGGED");
-  const bool seg4 = f && strcmp(f, "seg4") == 0;
-  const bool rx = mode == YU_MODE_VERIFY_RX;  // only k_seg verifies whole datagrams
-  const bool dg = mode == YU_MODE_TX_DATAGRAM;  // and fills both fields of one
-  const Variant &loop = rx ? kLoopRx : (dg ? kLoopDg : (mode == YU_MODE_RAW ? kLoopBE : kLoopLE));  // BE: exact past 131072 B
-  const Variant &c16 = rx ? kSegRx8c16 : (dg ? kSegDg8c16 : (mode_is_tx(mode) ? kSegTx8c16 : kSeg8c16));
-  if (f && strcmp(f, "loop") == 0) return loop;
-  if (f && strcmp(f, "rag") == 0 && !rx && !dg) return kRag;
-  if (mode_is_ipv4(mode)) return kHdr;  // header-only: one lane per packet
-  if (f && strcmp(f, "seg16") == 0) return c16;
-  if (n <= kSmallBurst && !f) return loop;
-  // up to 64K packets: 16-packet chunks, 4x the waves (U{64..1500}: 8192
-  // packets 11.2 -> 6.3 us, 32768 11.7 -> 8.7; U{40..200} 5.1 -> 4.4; jumbo
-  // 44.2 -> 17.0; VERIFY_RX 13.3 -> 7.1); from 65536 on 64-packet chunks win
-  // again (13.1 vs 14.7 us; profiles/r01/kbench_kseg_chunk16_sweep.log)
-  if (n < kMidBatch && !f) return c16;
-  return seg_for(!seg4, mode);
-}
-
-// Tuning override (measurement only, read under YU_TUNING=1: yu::tuning_env):
-// YU_VARIANT=<name> forces a k_small variant whenever it covers the shape.
-const char *forced_variant() {
-  static const char *v = yu::tuning_env("YU_VARIANT");
-  return v;
-}
-
-const Variant &pick_uniform(uint64_t base, uint64_t stride, uint32_t len,
-                            uint64_t n, int mode) {
-  const uint64_t need = mode_is_ipv4(mode) ? (len < 60u ? len : 60u) : len;
-  // the window starts at floor4(start): up to 3 extra bytes in front
-  const bool aligned4 = ((base | (n > 1 ? stride : 0)) & 3u) == 0;
-  const uint64_t span = need + (aligned4 ? 0 : 3);
-  // lane window offsets are 32-bit: (64/G - 1) strides + the window
-  auto fits = [&](const Variant &v) {
-    return span <= v.window && v.ppw * stride + v.window < kOOB;
-  };
-  // k_tiny: no junk bytes (4-aligned starts, no TX field, no IPv4 header walk)
-  const bool tiny_ok = aligned4 && !mode_is_ipv4(mode) && mode != YU_MODE_VERIFY_RX &&
-                       mode != YU_MODE_TX_DATAGRAM;
-  // k_lane: the same modes, one wave step = 64 whole strides in LDS, so only
-  // where gaps between packets waste at most half the bytes it loads
-  auto lane_fits = [&](const Variant &v) {
-    return tiny_ok && (stride & 3u) == 0 && len >= 1u && len <= stride && stride <= v.window &&
-           2u * stride <= 3u * (uint64_t)len;
-  };
-  if (mode == YU_MODE_VERIFY_RX || mode == YU_MODE_TX_DATAGRAM) {
-    // k_seg's RX / DG kinds keep positions in 32 bits: a 64-packet chunk must
-    // span less than 2 GiB, so sparser uniform batches take a wave per datagram
-    if (n > 1 && stride > kSeg32Stride) return mode == YU_MODE_VERIFY_RX ? kLoopRx : kLoopDg;
-    return pick_ragged(mode, n);
-  }
-  // IPv4 header-only modes: one lane per packet (1M x 1500-B datagrams:
-  // 29.9 us vs 36.9 with k_small<4,1>, kbench 13)
-  if (mode_is_ipv4(mode) && !forced_variant()) return kHdr;
-  if (const char *f = forced_variant()) {
-    if (!mode_is_ipv4(mode) && strncmp(f, "k_seg<", 6) == 0 && (n < 2 || stride <= kSeg32Stride))
-      return seg_for(f[6] == '8', mode);
-    if (mode_is_ipv4(mode) && strcmp(f, kHdr.name) == 0) return kHdr;
-    for (const Variant &v : kSmall)
-      if (strcmp(v.name, f) == 0 && fits(v)) return v;
-    for (const Variant &v : kTiny)
-      if (strcmp(v.name, f) == 0 && tiny_ok && fits(v)) return v;
-    for (const Variant &v : kLane)
-      if (strcmp(v.name, f) == 0 && lane_fits(v)) return v;
-  }
-  // k_lane up to 112 bytes (72-byte UDP datagrams: 16.4 vs 20.0 us with
-  // k_tiny<8>; 64-byte packets, config 2: 14.2 vs 14.8 with k_tiny<4>),
-  // k_tiny<8> above, where all its lanes load (128 bytes: 23.6 vs 24.6 us;
-  // tools/kbench 2 and 14); k_tiny<4> for sparse small packets
-  if (len <= 112u)
-    for (const Variant &v : kLane)
-      if (lane_fits(v)) return v;
-  if (tiny_ok)
-    for (const Variant &v : kTiny)
-      if (fits(v)) return v;
-  // Dense packets up to 704 bytes that k_lane / k_tiny do not take (129..704
-  // bytes, or not 4-aligned): the segmented stream sum beats per-packet lane
-  // groups, whose loads scatter over partly used windows (160 B: 34.6 vs 50.0 us;
-  // 320: 58-66 vs 88-89; 512: 87 vs 103; 704: 116 vs 120; unaligned 66 B: 26.8
-  // vs 38.6; from 768 on k_small is as fast or faster; tools/kbench 14,
-  // profiles/r01/kbench_uniform_size_sweep.log)
-  // (k_seg gives one wave to 64 packets: only batches of 64K packets or more
-  // have enough of them to fill the GPU; smaller ones keep the per-packet shapes)
-  const bool dense = 2u * stride <= 3u * (uint64_t)len && n >= kMidBatch;
-  if (len <= 704u && dense) return seg_for(len >= 448u, mode);
-  // and above 3 KiB, where it streams 8 KiB tiles past k_small<64,4> and the
-  // one-wave-per-packet k_loop (4096 B: 636 vs 664 us; 9000 B: 1373 vs 1464;
-  // 16 KiB: 0.88 vs 0.81 of peak) — given enough 64-packet chunks to fill the
-  // GPU (one wave each); a few huge packets keep k_loop's wave per packet
-  if (len > 3072u && dense) return seg_for(true, mode);
-  for (const Variant &v : kSmall)
-    if (fits(v)) return v;
-  return len > kLEMax ? kLoopBE : kLoopLE;
-}
-
-bool is_tiny(const Variant &v) { return v.ppw == 64u && v.G < 64u; }
 
 std::atomic<int> g_cu_count[64];
 
@@ -2545,76 +2161,6 @@ int cu_count(int dev) {
   return c;
 }
 
-// Tuning knobs (read once, measurement only, and only under YU_TUNING=1:
-// yu::tuning_env). YU_BLOCKS_PER_CU: grid size in 256-thread blocks per CU;
-// YU_NT: load policy 0/1/2 (see bld16).
-int env_int(const char *name, int lo, int hi, int dflt) {
-  const char *s = yu::tuning_env(name);
-  if (!s || !*s) return dflt;
-  int x = atoi(s);
-  return (x >= lo && x <= hi) ? x : dflt;
-}
-
-// Grid size in 256-thread blocks per CU. The grid is deliberately larger than
-// what is resident at once (5-8 blocks/CU): finished blocks are replaced by
-// fresh ones, which evens out the per-CU tail. Measured optimum on MI355X
-// (tools/kbench, round 1): 64 for MTU-size and larger packets, 16 for the
-// small-packet lane-group variants (G < 16). The 64-packet-step kernels
-// (k_lane, k_tiny: `step64`) run best on 6 (round 2, each wave then streams
-// about 4 steps with the next in flight): 1M x 64 B 14.2 -> 13.4 us, 72 B 16.0
-// -> 14.8, 32 B 10.4 -> 8.4, 100 B 21.7 -> 20.8, 124 B 25.0 -> 23.8
-// (profiles/r02/kbench_ab_lane_grid.log).
-// Uniform batches on 4 KiB k_seg tiles (dense 129..447-byte packets, `seg4u`)
-// run on 10: each wave then streams 2-3 chunks with the next tile in flight
-// instead of one chunk per wave (1M UDP datagrams, medians of 6 launches of
-// 30: 136 B 33.0 -> 30.5 us, 160 B 34.5 -> 32.9, 256 B 50.2 -> 47.8, 320 B
-// 58.8 -> 56.9, 384 B 70.3 -> 66.7, 200 and 420 B within 1 %;
-// profiles/r02/kbench_grid_mid_uniform_{a,b}.log).
-int blocks_per_cu(uint32_t G, bool step64, bool seg4u) {
-  static int v = env_int("YU_BLOCKS_PER_CU", 1, 1024, 0);
-  if (v) return v;
-  if (seg4u) return 10;
-  return step64 ? 6 : (G < 16 ? 16 : 64);
-}
-
-int use_nt() {
-  static int v = env_int("YU_NT", 0, 2, 2);
-  return v;
-}
-
-// k_small writing the field in place loads plainly unless YU_NT says otherwise: the
-// field's line is then more often still cached when the 2-byte store reaches it
-// (config 9: 320.9 -> 312.2 us on one box, 326.2 -> 321.2 on another; all-nt 330.2;
-// k_lane's 72-byte writer gains nothing, 29.9 vs 30.8; profiles/r03/kbench_ab_fill_nt.log)
-int fill_nt() {
-  static int v = env_int("YU_NT", 0, 2, 0);
-  return v;
-}
-
-// The ragged in-place writer of k_seg's TX kind (wbk): 0 = one 2-byte store per
-// field; 1 = the fields patched into the parked tile and their 128-byte lines
-// stored whole. YU_FILL_WB overrides.
-int fill_wb() {
-  static int v = env_int("YU_FILL_WB", 0, 1, 1);
-  return v;
-}
-
-// YU_XCD: 1 = XCD-aware block order (grid_wave), 0 (default) = plain blockIdx.
-// Measured (round 1, tools/ab.sh): no gain on any config — these kernels
-// share at most one line between neighbouring blocks, and the Infinity Cache
-// already absorbs its second fetch — and -1..3 % on configs 2/3, so it is off.
-// YU_SEG_SMALL_BLOCKS: blocks per CU that work on a small-packet ragged
-// batch (seg_waves); 0 = the whole grid.
-int seg_small_blocks() {
-  static int v = env_int("YU_SEG_SMALL_BLOCKS", 0, 64, 3);
-  return v;
-}
-
-int use_xcd() {
-  static int v = env_int("YU_XCD", 0, 1, 0);
-  return v;
-}
-
 int hip_status(hipError_t e) {
   if (e == hipSuccess) return YU_OK;
   if (e == hipErrorNoDevice || e == hipErrorInvalidDevice) return YU_ENODEV;
@@ -2622,38 +2168,22 @@ int hip_status(hipError_t e) {
   return YU_EHIP_BASE - (int)e;
 }
 
-int launch(const Variant &v, const BatchArgs &A, hipStream_t stream) {
+int launch(const yu::Shape &s, const BatchArgs &A, hipStream_t stream) {
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return hip_status(e);
-  const uint64_t waves_per_block = 4;
-  const bool seg4u = !A.offsets && (&v == &kSeg4 || &v == &kSegTx4);
-  const uint64_t cap = (uint64_t)cu_count(dev) * (uint64_t)blocks_per_cu(v.G, is_tiny(v), seg4u);
-  // k_small: runs from 8 runs per CU up (1500-B packets, runs vs interleaved:
-  // 16384 packets 8.0 vs 7.2 us, 32768 11.3 vs 12.5, 131072 35.3 vs 38.8; 768-B
-  // packets 6.6 vs 5.0, 7.5 vs 8.2, 19.7 vs 22.0; kbench_ab_k_small_runs.log)
-  // (YU_RUNS: 0 never, 2 whenever not filling — measurement only)
-  static const int runs_knob = env_int("YU_RUNS", 0, 2, 1);
-  const bool runs = v.run && !A.fill &&
-                    (runs_knob == 2 || (runs_knob == 1 && A.n / v.run >= 8u * (uint64_t)cu_count(dev)));
-  const uint64_t ppw = runs ? v.run : v.ppw;
-  uint64_t waves = (A.n + ppw - 1) / ppw;
-  uint64_t blocks = (waves + waves_per_block - 1) / waves_per_block;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
+  const yu::Plan p = yu::plan(s, cu_count(dev), yu::env_knobs());
   BatchArgs a = A;
-  a.xcd = (uint32_t)use_xcd();
-  a.small_waves = (uint32_t)cu_count(dev) * 4u * (uint32_t)seg_small_blocks();
-  KernelFn k = A.fill && v.fill ? v.fill : v.fn[use_nt()];
-  if (v.run && !runs) k = v.inter[A.fill ? fill_nt() : use_nt()];
-  // TX_DATAGRAM in place loads plainly too (fill_nt): a datagram's header line is
-  // then more often still cached when its two field stores arrive (1M datagrams
-  // U{40..1500}: 211.5 -> 203.1 us; the TXW kind is better off non-temporal, 48.7
-  // vs 52.1 us; profiles/r04/kbench_ab_r04k_fill_nt.log)
-  if (A.fill && (&v == &kSegDg8 || &v == &kSegDg8c16 || &v == &kSegDg8c40))
-    k = v.fn[fill_nt()];
-  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+  a.uf = p.uf;
+  a.xcd = p.xcd;
+  a.small_waves = p.small_waves;
+  hipLaunchKernelGGL(kernel_fn(p), dim3(p.blocks), dim3(256), 0, stream, a);
   return hip_status(hipGetLastError());
+}
+
+// The yu_*_variant* calls: the plan's kernel name (no CU count enters that).
+const char *variant_name(const yu::Shape &s) {
+  return yu::plan(s, 256, yu::env_knobs()).name;
 }
 
 bool aligned(const void *p, uintptr_t a) {
@@ -2669,20 +2199,6 @@ int check_common(int mode, const uint16_t *initial_arr, const uint8_t *addrs,
   if (addrs && !aligned(addrs, 4)) return YU_EINVAL;              // EINVAL:side-align
   if (out && !aligned(out, 2)) return YU_EINVAL;                  // EINVAL:side-align
   return YU_OK;
-}
-
-// Ragged in place: the TX kinds of k_seg take their TXW form (the whole-line
-// write-back, 1M UDP datagrams U{40..200}: 67.5 -> 48.9 us, kbench 8, DESIGN.md
-// §5.4) unless YU_FILL_WB=0.
-const Variant &pick_ragged_fill(int mode, uint64_t n, bool fill) {
-  const Variant &v = pick_ragged(mode, n);
-  if (fill && &v == &kSegDg8)
-    return kSegDg8c40;
-  if (!fill || !fill_wb()) return v;
-  if (&v == &kSegTx8) return kSegTxW8c48;
-  if (&v == &kSegTx8c16) return kSegTxW8c16;
-  if (&v == &kSegTx4) return kSegTxW4;
-  return v;
 }
 
 int batch_uniform(const uint8_t *data, uint8_t *fill, uint64_t stride,
@@ -2716,12 +2232,7 @@ int batch_uniform(const uint8_t *data, uint8_t *fill, uint64_t stride,
   A.len = len;
   A.initial = initial;
   A.mode = mode;
-  const Variant &v = pick_uniform((uintptr_t)data, stride, len, n, mode);
-  if (is_tiny(v))
-    A.uf = len >= 16u * v.G ? 1u : 0u;  // k_tiny: all chunks whole?
-  else
-    A.uf = v.window ? (mode_is_ipv4(mode) ? 0u : len / (16u * v.G)) : 0u;
-  return launch(v, A, (hipStream_t)stream);
+  return launch({false, (uintptr_t)data, stride, len, n, mode, fill != nullptr}, A, (hipStream_t)stream);
 }
 
 int batch_ragged(const uint8_t *data, uint8_t *fill, const uint64_t *offsets,
@@ -2748,8 +2259,8 @@ int batch_ragged(const uint8_t *data, uint8_t *fill, const uint64_t *offsets,
   A.uf = 0;
   A.mode = mode;
   // k_seg streams the batch's bytes (exact BE recovery for chunks holding a
-  // RAW packet > 131072 bytes); k_rag takes the IPv4 header-only modes.
-  return launch(pick_ragged_fill(mode, n, fill != nullptr), A, (hipStream_t)stream);
+  // RAW packet > 131072 bytes); k_hdr takes the IPv4 header-only modes.
+  return launch({true, 0, 0, 0, n, mode, fill != nullptr}, A, (hipStream_t)stream);
 }
 
 // Completion signal for the host path's direct mode (yucsum_internal.h):
@@ -2808,28 +2319,28 @@ int yu_csum_fill_ragged(uint8_t *data, const uint64_t *offsets, uint64_t n,
 
 const char *yu_uniform_variant(uint64_t stride, uint32_t len, int mode,
                                uint64_t data_align16) {
-  return pick_uniform(data_align16 & 15u, stride, len, 2, mode).name;
+  return variant_name({false, data_align16 & 15u, stride, len, 2, mode, false});
 }
 
 const char *yu_uniform_variant_n(uint64_t stride, uint32_t len, uint64_t n, int mode,
                                  uint64_t data_align16) {
   if (mode < 0 || mode >= YU_MODE_COUNT) return "";
-  return pick_uniform(data_align16 & 15u, stride, len, n, mode).name;
+  return variant_name({false, data_align16 & 15u, stride, len, n, mode, false});
 }
 
 const char *yu_ragged_variant(int mode) {
   if (mode < 0 || mode >= YU_MODE_COUNT) return "";
-  return pick_ragged(mode, 1u << 20).name;
+  return variant_name({true, 0, 0, 0, 1u << 20, mode, false});
 }
 
 const char *yu_ragged_variant_n(int mode, uint64_t n) {
   if (mode < 0 || mode >= YU_MODE_COUNT) return "";
-  return pick_ragged(mode, n).name;
+  return variant_name({true, 0, 0, 0, n, mode, false});
 }
 
 const char *yu_ragged_fill_variant_n(int mode, uint64_t n) {
   if (mode < 0 || mode >= YU_MODE_COUNT) return "";
-  return pick_ragged_fill(mode, n, true).name;
+  return variant_name({true, 0, 0, 0, n, mode, true});
 }
 
 int yu_device_count(void) {
