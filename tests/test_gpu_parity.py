@@ -1517,3 +1517,162 @@ def test_ragged_batch_size_cutovers(dev, oracle_c, mode):
                                     addrs=None if addrs is None else _to(dev, addrs)).cpu().numpy()
         want_v = oracle_c.batch(blob, mode, offsets=offs, addrs=addrs, threads=8)
         assert np.array_equal(got, want_v), (mode, npk, np.nonzero(got != want_v)[0][:8])
+
+
+# ---------------------------------------------------------------------------
+# Uniform batches on k_seg (dense, 65536 packets and more) and overlapping packets
+# ---------------------------------------------------------------------------
+_NOISE = None
+_SEG_COUNTS = (65536, 65537, 65599)  # whole 64-packet chunks, and 1 and 63 packets in the last
+
+
+def _noise(nbytes, shift=0):
+    """`nbytes` of fixed random bytes: a 1048573-byte block (a prime, so no packet
+    stride divides it) drawn once and repeated, from `shift` on."""
+    global _NOISE
+    if _NOISE is None:
+        _NOISE = np.random.default_rng(65536).integers(0, 256, size=1048573, dtype=np.uint8)
+    return np.resize(np.roll(_NOISE, -shift), nbytes)
+
+
+def _seg_name(length, tx):
+    return f"k_seg<{4 if length < 448 else 8}{',tx' if tx else ''}>"
+
+
+@pytest.mark.parametrize("L,stride", [(136, 136), (300, 448), (448, 448), (700, 1048), (3076, 3076)])
+@pytest.mark.parametrize("mode", [O.MODE_UDP, O.MODE_TCP, O.MODE_ICMP])
+def test_uniform_k_seg_in_place(dev, oracle_c, mode, L, stride):
+    """A uniform batch written in place by k_seg's TX kind (dense, 4-aligned, 65536
+    packets and more; both tile sizes): the device view starts at 0, 4, 60 and 124 mod
+    128, with whole chunks and 1 and 63 packets in the last one. Afterwards every byte but
+    the fields equals the input (the gaps between packets and the bytes before and after
+    the batch too), the fields and results equal the oracle's, and the matching verify
+    mode accepts every packet."""
+    f = {O.MODE_UDP: 6, O.MODE_TCP: 16, O.MODE_ICMP: 2}[mode]
+    name = {O.MODE_UDP: "udp", O.MODE_TCP: "tcp", O.MODE_ICMP: "icmp"}[mode]
+    nmax = max(_SEG_COUNTS)
+    for base in (0, 4, 60, 124):
+        host = _noise(base + (nmax - 1) * stride + L + 128, shift=1000 * mode + base)
+        starts = base + np.arange(nmax, dtype=np.int64) * stride
+        if mode == O.MODE_TCP:  # DataOffset 5 (sendTCP's segments)
+            host[starts + 12] = 0x50
+        addrs = _noise(8 * nmax, shift=7 * L) if mode != O.MODE_ICMP else None
+        a = None if addrs is None else _to(dev, addrs)
+        # (a packet's result does not depend on the batch size: one oracle run for the three counts)
+        want_all = oracle_c.batch(host[base:], mode, stride=stride, length=L, n=nmax, addrs=addrs, threads=8)
+        for n in _SEG_COUNTS:
+            assert FORCED or batch.variant(stride, L, name, base, n=n) == _seg_name(L, True)
+            want = want_all[:n]
+            dfull = _to(dev, host)
+            assert dfull.data_ptr() % 128 == 0
+            out = batch.checksum_uniform(dfull[base:], stride, L, n, mode, addrs=a, fill=True).cpu().numpy()
+            assert np.array_equal(out, want), (base, n, np.nonzero(out != want)[0][:8])
+            expect = host.copy()  # the packets past n, the gaps and the bytes around the batch stay
+            expect[starts[:n] + f] = (want >> 8).astype(np.uint8)
+            expect[starts[:n] + f + 1] = (want & 0xFF).astype(np.uint8)
+            bad = np.nonzero(dfull.cpu().numpy() != expect)[0]
+            assert bad.size == 0, (base, n, bad[:8])
+            if mode == O.MODE_ICMP:  # a filled ICMP message sums to 0xFFFF (header/icmpv4.go:46-48)
+                v = batch.checksum_uniform(dfull[base:], stride, L, n, O.MODE_RAW)
+            else:
+                v = batch.checksum_uniform(dfull[base:], stride, L, n,
+                                           O.MODE_VERIFY_UDP if mode == O.MODE_UDP else O.MODE_VERIFY_TCP, addrs=a)
+            assert bool(batch.verified(v).all()), (base, n)
+
+
+@pytest.mark.parametrize("L,stride", [(66, 66), (129, 193), (447, 670), (448, 449), (704, 1056), (3073, 4609)])
+@pytest.mark.parametrize("mode,side", [(O.MODE_RAW, "init"), (O.MODE_UDP, "addrs"), (O.MODE_VERIFY_TCP, "addrs"),
+                                       (O.MODE_ICMP, "scalar")])
+def test_uniform_k_seg_gaps_and_alignment(dev, oracle_c, mode, side, L, stride):
+    """Uniform batches on k_seg with gaps between the packets (len < stride <= 1.5 len:
+    bytes that are streamed and belong to no packet), at base offsets 0-3, on random,
+    all-zero and all-ones bytes, with whole chunks and 1 and 63 packets in the last one.
+    Results only."""
+    tx = mode in (O.MODE_UDP, O.MODE_ICMP)
+    name = {O.MODE_RAW: "raw", O.MODE_UDP: "udp", O.MODE_VERIFY_TCP: "verify_tcp", O.MODE_ICMP: "icmp"}[mode]
+    nmax = max(_SEG_COUNTS)
+    addrs = _noise(8 * nmax, shift=3 * L) if side == "addrs" else None
+    init = _noise(2 * nmax, shift=5 * L).view(np.uint16) if side == "init" else None
+    initial = 0xBEEF if side == "scalar" else 0
+    d_addrs = None if addrs is None else _to(dev, addrs)
+    d_init = None if init is None else _to(dev, init)
+    for base in range(4):
+        for kind in ("rand", "zero", "ff"):
+            total = base + (nmax - 1) * stride + L + 64
+            host = _noise(total, shift=L + base) if kind == "rand" else _rand(None, total, kind)
+            if mode == O.MODE_VERIFY_TCP:
+                host[base + np.arange(nmax, dtype=np.int64) * stride + 12] = 0x50
+            # (a packet's result does not depend on the batch size: one oracle run for the three counts)
+            want = oracle_c.batch(host[base:], mode, stride=stride, length=L, n=nmax, initial_arr=init,
+                                  initial=initial, addrs=addrs, threads=8)
+            d = _to(dev, host)
+            for n in _SEG_COUNTS:
+                assert FORCED or batch.variant(stride, L, name, base, n=n) == _seg_name(L, tx)
+                got = batch.checksum_uniform(d[base:], stride, L, n, mode, initial=initial, initial_arr=d_init,
+                                             addrs=d_addrs).cpu().numpy()
+                assert np.array_equal(got, want[:n]), (base, n, kind, np.nonzero(got != want[:n])[0][:8])
+
+
+@pytest.mark.parametrize("L", [705, 3072])
+def test_uniform_dense_batches_that_stay_on_k_small(dev, oracle_c, L):
+    """Each side of k_seg's length ranges: dense 705- and 3072-byte packets keep k_small
+    at 65536 packets and more."""
+    n = 65537
+    assert batch.variant(L, L, "raw", 0, n=n).startswith("k_small<")
+    host = _noise(n * L, shift=L)
+    init = _noise(2 * n).view(np.uint16)
+    got = batch.checksum_uniform(_to(dev, host), L, L, n, "raw", initial_arr=_to(dev, init)).cpu().numpy()
+    assert np.array_equal(got, oracle_c.batch(host, O.MODE_RAW, stride=L, length=L, n=n, initial_arr=init, threads=8))
+
+
+_BIG_N = 65536 + 63
+_OVERLAP = [  # mode, len, stride, n (None: 16 * 8 * CUs + 5, k_small's runs), kernel
+    ("raw", 100, 4, 1000, "k_tiny<8>"), ("udp", 100, 4, 1000, "k_tiny<8>"),
+    ("tcp", 1500, 64, 1000, "k_small<16,6>"), ("raw", 200, 1, 1000, "k_small<8,2>"),
+    ("udp", 1500, 8, None, "k_small<16,6>"),
+    ("ipv4", 40, 4, 1000, "k_hdr"),
+    ("raw", 70000, 3, 300, "k_loop<4,LE>"),
+    ("raw", 131073, 1, 300, "k_loop<4,BE>"),
+    ("raw", 300, 4, _BIG_N, "k_seg<4>"), ("udp", 600, 8, _BIG_N, "k_seg<8,tx>"),
+    ("raw", 131075, 8, _BIG_N, "k_seg<8>"),  # the exact big-endian path on a uniform batch
+    ("raw", 500, 0, _BIG_N, "k_seg<8>"),
+]
+
+
+_OVERLAP += [(m, None, 0, n, k.format("rx" if m == "verify_rx" else "dg"))  # one datagram, n times
+             for m in ("verify_rx", "tx_datagram")
+             for n, k in ((100, "k_loop<4,{}>"), (5000, "k_seg<8,{},c16>"), (65536, "k_seg<8,{}>"))]
+
+
+@pytest.mark.parametrize("mode,L,stride,n,kern", _OVERLAP)
+def test_uniform_overlapping_packets(dev, oracle_c, mode, L, stride, n, kern):
+    """include/yucsum.h: "Packets may overlap (stride < len) - they are only read". The
+    planner treats every overlapping batch as dense; each family it picks, on a few
+    hundred KB of data, and stride = 0 (every packet the same bytes) down to the
+    datagram modes' kernels. Results only."""
+    if n is None:
+        n = 16 * 8 * torch.cuda.get_device_properties(dev).multi_processor_count + 5
+    m = batch.MODES[mode]
+    if L is None:
+        import rxgen
+        rng = np.random.default_rng(700 + n)
+        pk = (rxgen.make_packet(rng, 180, proto=6, ihl=6) if mode == "verify_rx"
+              else rxgen.tx_packet(rng, 180, proto=17, ihl=6))
+        L = len(pk)
+        host = np.concatenate([np.frombuffer(bytes(pk), np.uint8), np.zeros(64, np.uint8)])
+    else:
+        host = _noise((n - 1) * stride + L + 64, shift=L)
+    assert FORCED or batch.variant(stride, L, mode, 0, n=n) == kern
+    starts = np.arange(n, dtype=np.int64) * stride
+    if mode == "tcp":
+        host[starts + 12] = 0x50
+    if mode == "ipv4":
+        host[starts] = 0x45 + (starts // 4 % 6).astype(np.uint8)  # IHL 5..10: headers within the 40 bytes
+    addrs = _noise(8 * n, shift=11) if mode in ("udp", "tcp") else None
+    init = _noise(2 * n, shift=13).view(np.uint16) if mode == "raw" else None
+    got = batch.checksum_uniform(_to(dev, host), stride, L, n, m, addrs=None if addrs is None else _to(dev, addrs),
+                                 initial_arr=None if init is None else _to(dev, init)).cpu().numpy()
+    want = oracle_c.batch(host, m, stride=stride, length=L, n=n, addrs=addrs, initial_arr=init, threads=8)
+    assert np.array_equal(got, want), np.nonzero(got != want)[0][:8]
+    if mode in ("verify_rx", "tx_datagram"):
+        assert want.all()  # a well-formed datagram: RX flags / both fields, in every slot
