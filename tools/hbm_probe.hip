@@ -4,6 +4,8 @@
 // rule 10). Grid-stride dwordx4 loads, U loads in flight per lane, one
 // 4-byte store per thread (negligible).
 //
+// PROBE_RUNS=1: k_small<16,6>'s two request shapes for config 3 (read_runs).
+//
 // build: hipcc --offload-arch=gfx950 -O3 tools/hbm_probe.hip -o tools/hbm_probe
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -100,6 +102,74 @@ __global__ __launch_bounds__(256) void read_tile(const uint4 *__restrict__ p, ui
   out[blockIdx.x * blockDim.x + threadIdx.x] = acc;
 }
 
+// k_small<16,6>'s run shape on a dense batch of 1500-byte packets (config 3): a
+// wave takes runs of 16 packets in 4 steps of 4, the next step's 6 loads per lane
+// issued before the current step is summed, through a buffer descriptor based at
+// the step; the first and last load of a step are plain, the others nt (load
+// policy 2). Only the request shape differs:
+//   DENSE = false ("win"): groups of 16 lanes, group g's load u takes the 256 B at
+//     floor4(start of packet g) + 256u; lanes past the packet's end do not load.
+//   DENSE = true ("dense"): load u takes the aligned KiB u of the step's range
+//     from floor128(step start) on, up to the last line the step touches.
+template <bool DENSE>
+__global__ __launch_bounds__(256) void read_runs(const uint8_t *__restrict__ p, uint64_t npk, uint32_t *out) {
+  constexpr uint32_t L = 1500u, OOB = 0x80000000u;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const uint64_t nw = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  const uint64_t nsteps = npk / 16u * 4u;  // whole runs only
+  const uint64_t end = (uint64_t)(uintptr_t)p + npk * L;
+  uint32_t acc = 0;
+  // step t of this wave: run wave + (t / 4) * nw, packets 4 * (t % 4) on
+  auto first = [&](uint64_t t) -> uint64_t { return (wave + (t >> 2) * nw) * 16u + (t & 3u) * 4u; };
+  auto ld = [&](uint64_t pb, bool live, uint4 (&c)[6]) __attribute__((always_inline)) {
+    const uint64_t start = (uint64_t)(uintptr_t)p + pb * L;
+    uint64_t base = DENSE ? start & ~127ull : start & ~3ull;
+    // wave-uniform, in SGPRs (the builtin returns int: widen it unsigned)
+    const uint32_t blo = __builtin_amdgcn_readfirstlane((uint32_t)base);
+    const uint32_t bhi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
+    base = ((uint64_t)bhi << 32) | blo;
+    const uint64_t n = end - base;
+    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
+        (void *)base, (short)0, (int)(n < OOB ? n : OOB), 0x00020000);
+    const uint32_t hi = ((uint32_t)(start - base) + 4u * L + 127u) & ~127u;
+#pragma unroll
+    for (int u = 0; u < 6; ++u) {
+      uint32_t off;
+      if (DENSE) {
+        off = 1024u * u + 16u * lane;
+        off = off < hi ? off : OOB;
+      } else {
+        const uint32_t cr = 16u * ((lane & 15u) + 16u * u);
+        off = cr < L ? (lane >> 4) * L + cr : OOB;
+      }
+      off = live ? off : OOB;  // a wave's last step prefetches nothing
+      const u32x4 v = (u != 0 && u != 5) ? __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 2)
+                                         : __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
+      c[u] = make_uint4(v.x, v.y, v.z, v.w);
+    }
+  };
+  uint64_t t = 0;
+  auto step = [&](const uint4 (&c)[6], uint4 (&cn)[6]) __attribute__((always_inline)) -> bool {
+    const uint64_t pn = first(t + 1);
+    const bool more = pn < nsteps * 4u;
+    ld(more ? pn : first(t), more, cn);
+#pragma unroll
+    for (int u = 0; u < 6; ++u) acc += c[u].x + c[u].y + c[u].z + c[u].w;
+    ++t;
+    return more;
+  };
+  if (first(0) < nsteps * 4u) {
+    uint4 a[6], b[6];
+    ld(first(0), true, a);
+    for (;;) {
+      if (!step(a, b)) break;
+      if (!step(b, a)) break;
+    }
+  }
+  out[blockIdx.x * blockDim.x + threadIdx.x] = acc;
+}
+
 __global__ void fill(uint4 *p, uint64_t n16) {
   uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (; i < n16; i += (uint64_t)gridDim.x * blockDim.x) {
@@ -157,6 +227,34 @@ int main(int argc, char **argv) {
           printf("round %d %-16s blocks/CU %2d: %7.1f us  %7.1f GB/s\n", r, ks[i].name, bpc, sec * 1e6,
                  n16 * 16 / sec / 1e9);
         }
+    return 0;
+  }
+  if (getenv("PROBE_RUNS")) {  // k_small<16,6>'s request shapes on its grid, against a plain read
+    const uint64_t npk = bytes / 1500u;
+    struct M { const char *name; int which, bpc; } ms[] = {
+        {"win", 0, 64}, {"read U4 nt", 2, 2}, {"dense", 1, 64}, {"read U4 nt", 2, 2}};
+    printf("buffer %.3f GB x %d rotating, %d CUs, %llu packets of 1500 B\n", bytes / 1e9, nbuf, cus,
+           (unsigned long long)npk);
+    for (int r = 0; r < rounds; ++r)
+      for (auto &m : ms) {
+        const int grid = cus * m.bpc;
+        auto go = [&](int b) {
+          if (m.which == 0) read_runs<false><<<grid, 256>>>((const uint8_t *)buf[b], npk, out);
+          else if (m.which == 1) read_runs<true><<<grid, 256>>>((const uint8_t *)buf[b], npk, out);
+          else read_sum<4, true><<<grid, 256>>>(buf[b], n16, out);
+        };
+        for (int w = 0; w < 3; ++w) go(w % nbuf);
+        CK(hipEventRecord(e0));
+        for (int k = 0; k < reps; ++k) go(k % nbuf);
+        CK(hipEventRecord(e1));
+        CK(hipEventSynchronize(e1));
+        CK(hipGetLastError());
+        float ms_;
+        CK(hipEventElapsedTime(&ms_, e0, e1));
+        const double sec = ms_ / 1e3 / reps;
+        const double by = m.which == 2 ? n16 * 16.0 : npk / 16 * 16 * 1500.0;
+        printf("round %d %-12s blocks/CU %2d: %7.1f us  %7.1f GB/s\n", r, m.name, m.bpc, sec * 1e6, by / sec / 1e9);
+      }
     return 0;
   }
   int bpcs[] = {2, 4, 8, 16};

@@ -58,6 +58,8 @@
 //     sparse ones). A wave holds 64/G packets per step; each group of G lanes
 //     loads its packet window in U dwordx4 loads per lane, reduces with log2(G)
 //     DPP adds and its last lane finishes the packet (config 3: k_small<16,6>).
+//     Dense read-only batches on k_small<16,6> load a step's packets as whole
+//     128-byte lines and repack them through LDS instead (yucsum_dense.h).
 //   k_seg<U, NT, K, CH>: ragged batches of more than 4096 packets, VERIFY_RX,
 //     and dense uniform packets of other sizes: a segmented sum over the byte
 //     stream of CH consecutive packets per wave (64, or 16 below 64K packets),
@@ -79,6 +81,7 @@
 #include <type_traits>
 
 #include "yucsum.h"
+#include "yucsum_dense.h"
 #include "yucsum_internal.h"
 #include "yucsum_plan.h"
 
@@ -476,6 +479,13 @@ __device__ __forceinline__ uint32_t ipv4_hl(uint32_t w0, uint32_t sh) {
   return ((w0 >> (8u * sh)) & 0xFu) * 4u;
 }
 
+// Orders one wave's LDS accesses (its slice is its own: no block barrier).
+__device__ __forceinline__ void wave_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // ---------------------------------------------------------------------
 // k_small<G, U, NT>: uniform stride, whole packet window in one step,
 // software-pipelined: the loads of step t+1 are issued before step t is
@@ -489,29 +499,78 @@ struct SmallItem {
 };
 
 // Fetch the windows of packets pb+gw (pb = the wave's first packet of the
-// step; pb >= n fetches nothing).
+// step; pb >= n fetches nothing). Dense (wave-uniform; yucsum_dense.h): the
+// same U loads per lane, but of the step's whole byte range, line-aligned:
+// c[u] then holds chunk 64u + lane of that range, and small_repack turns it
+// into the window's chunk before the step is summed.
 template <int G, int U, int NT, bool SIDE = true>
 __device__ __forceinline__ void small_fetch(const BatchArgs &A,
                                             const SidePtrs &sp, uint64_t pb,
                                             uint32_t gw, uint32_t gl, bool ipv4,
-                                            SmallItem<G, U> &it) {
+                                            bool dense, SmallItem<G, U> &it) {
   const uint64_t p = pb + gw;
   const bool active = p < A.n;
   const uint64_t data = (uint64_t)(uintptr_t)A.data;
-  const uint64_t base = uniform64((data + pb * A.stride) & ~3ull);
+  const uint64_t wbase = (data + pb * A.stride) & ~3ull;
   const uint64_t sabs = data + (active ? p : pb) * A.stride;
-  const uint32_t lw = (uint32_t)((sabs & ~3ull) - base);  // this group's window
   it.sh = (uint32_t)(sabs & 3u);
   it.len = active ? A.len : 0u;
   const uint32_t le = ipv4 ? (it.len < 60u ? it.len : 60u) : it.len;
-  const uint32_t eload = active ? it.sh + le : 0u;
-  const __amdgpu_buffer_rsrc_t r = rsrc_at(base, A.end);
+  // Load u of a lane is at x = x0 + u * dx of its range (this group's window),
+  // at buffer offset add + x if x < lim
+  uint64_t b = wbase;
+  uint32_t x0 = 16u * gl, dx = 16u * G;
+  uint32_t lim = active ? it.sh + le : 0u;
+  uint32_t add = (uint32_t)((sabs & ~3ull) - wbase);
+  if (yu::dense_inst(G, U) && dense) {  // the step's range, counted from ds.lo
+    const yu::DenseStep ds = yu::dense_step(data, A.len, A.n, pb, 64 / G);
+    b = ds.base;
+    x0 = yu::dense_x0(ds, gw * G + gl);
+    dx = yu::kDensePiece;
+    lim = yu::dense_lim(ds);
+    add = ds.lo;
+  }
+  const __amdgpu_buffer_rsrc_t r = rsrc_at(uniform64(b), A.end);
 #pragma unroll
   for (int u = 0; u < U; ++u) {
-    const uint32_t cr = 16u * (gl + (uint32_t)u * G);
-    it.c[u] = bld16(r, cr < eload ? lw + cr : kOOB, nt_step<NT>(u, U));
+    const uint32_t x = x0 + (uint32_t)u * dx;
+    it.c[u] = bld16(r, x < lim ? add + x : kOOB, nt_step<NT>(u, U));
   }
   if (SIDE) it.sd = load_side(sp, active ? p : A.n - 1);
+}
+
+// Dense fetch, second half: park the step's U pieces in the wave's LDS slice
+// (a mirror of the step's range) and read each group's window, which begins
+// `wo` bytes into the slice, back into the layout the window path loads: c[u]
+// = chunk gl + G*u of the window. A chunk holding the packet's end brings the
+// bytes after it along, as there; a chunk past the end, zero there, holds
+// whatever follows in LDS here: both are masked below (the packet starts
+// 4-aligned and is whole dwords, so sum_masked drops every dword from the end
+// on, and steps below uf hold no such chunk). W dwords per read: windows
+// start 4W-aligned (wave-uniform, see k_small). The last group's window may
+// reach past the slice, into those masked bytes: the next wave's slice, or
+// the array's pad (yu::dense_pad).
+template <int G, int U, int W>
+__device__ __forceinline__ void small_repack(SmallItem<G, U> &it, uint4 *slice, uint32_t wo,
+                                             uint32_t lane, uint32_t gl) {
+#pragma unroll
+  for (int u = 0; u < U; ++u) slice[64 * u + lane] = it.c[u];
+  wave_lds_fence();
+  const uint8_t *win = (const uint8_t *)slice + wo + 16u * gl;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const uint8_t *q = win + 16 * G * u;
+    if (W == 4) {
+      it.c[u] = *(const uint4 *)q;
+    } else if (W == 2) {
+      const uint2 a = *(const uint2 *)q, b = *(const uint2 *)(q + 8);
+      it.c[u] = make_uint4(a.x, a.y, b.x, b.y);
+    } else {
+      const uint32_t *d = (const uint32_t *)q;
+      it.c[u] = make_uint4(d[0], d[1], d[2], d[3]);
+    }
+  }
+  wave_lds_fence();  // the next step's stores stay behind these reads
 }
 
 // PR (packets per run): 0 = wave w's step t takes packets (w + t*waves)*GPW on
@@ -522,8 +581,11 @@ __device__ __forceinline__ void small_fetch(const BatchArgs &A,
 // (PR * 2 bytes) after its last step: per-step side loads and result stores
 // are small scattered requests, and a wave's loads return in order, so one
 // slow side load holds up the packet bytes behind it.
+// The dense instances are held to the 5 waves per SIMD (96 VGPRs) they had
+// before the repack, which the allocator otherwise gives up (113, 4 waves).
 template <int G, int U, int NT, int PR = 0>
-__global__ __launch_bounds__(256) void k_small(BatchArgs A) {
+__global__ __launch_bounds__(256)
+    __attribute__((amdgpu_waves_per_eu(yu::dense_inst(G, U) ? 5 : 1))) void k_small(BatchArgs A) {
   constexpr int GPW = 64 / G;
   constexpr int SPR = PR ? PR / GPW : 1;  // steps per run
   static_assert(PR == 0 || (PR % GPW == 0 && PR <= 64 && (SPR & (SPR - 1)) == 0),
@@ -537,6 +599,15 @@ __global__ __launch_bounds__(256) void k_small(BatchArgs A) {
   const bool ipv4 = mode_is_ipv4(mode);
   const SidePtrs sp = side_ptrs(A);
   const uint32_t uf = A.uf;
+  // Dense fetch (G, U of yu::dense_inst only: the others hold no LDS)
+  constexpr bool kDense = yu::dense_inst(G, U);
+  uint4 *slice = nullptr;
+  if constexpr (kDense) {
+    __shared__ uint4 park[4 * 64 * U + yu::dense_pad(G, U) / 16];
+    slice = park + 64 * U * __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  }
+  const bool dense = kDense && yu::dense_ok(G, U, (uint64_t)(uintptr_t)A.data, A.offsets != nullptr,
+                                            A.stride, A.len, A.fill != nullptr, ipv4);
   // first packet of the wave's step t
   auto first = [&](uint64_t t) -> uint64_t {
     if (PR == 0) return (wave + t * nwaves) * GPW;
@@ -568,13 +639,21 @@ __global__ __launch_bounds__(256) void k_small(BatchArgs A) {
   // finish its packets. Returns false when the wave has no next step. The
   // loop below alternates two items instead of copying nx into it: a copy
   // would wait for the prefetch to land before the back-edge.
-  auto step = [&](const SmallItem<G, U> &it, SmallItem<G, U> &nx) __attribute__((always_inline)) -> bool {
+  auto step = [&](SmallItem<G, U> &it, SmallItem<G, U> &nx) __attribute__((always_inline)) -> bool {
     const uint64_t pn = first(t + 1);
     const bool more = pn < A.n;  // wave-uniform
     const uint32_t k = (uint32_t)(t % SPR);
-    small_fetch<G, U, NT, PR == 0>(A, sp, more ? pn : A.n, gw, gl, ipv4, nx);
+    const uint64_t p = pb + gw;
+    small_fetch<G, U, NT, PR == 0>(A, sp, more ? pn : A.n, gw, gl, ipv4, dense, nx);
     if (PR && k == 0 && t) rs = nrs;  // after the prefetch: the copy waits for nrs only
     if (PR && k == SPR - 1 && more) run_side(pn, nrs);
+    if (kDense && dense) {
+      const uint32_t wo = p < A.n ? yu::dense_window((uint64_t)(uintptr_t)A.data, A.len, pb, gw) : 0u;
+      // widest LDS read the windows' alignment allows (data is 16-aligned)
+      if ((A.len & 15u) == 0) small_repack<G, U, 4>(it, slice, wo, lane, gl);
+      else if ((A.len & 7u) == 0) small_repack<G, U, 2>(it, slice, wo, lane, gl);
+      else small_repack<G, U, 1>(it, slice, wo, lane, gl);
+    }
 
     uint32_t E = it.sh + it.len;
     if (ipv4) {
@@ -593,7 +672,6 @@ __global__ __launch_bounds__(256) void k_small(BatchArgs A) {
       else
         acc = sum_masked<false>(it.c[u], cr, lim, tm, 0u, acc);
     }
-    const uint64_t p = pb + gw;
     const Junk j = make_junk(it.sh, E, mode);
     uint32_t jx[3] = {0u, 0u, 0u};
     if (PR && kDppSide) {
@@ -645,7 +723,7 @@ __global__ __launch_bounds__(256) void k_small(BatchArgs A) {
     return more;
   };
   SmallItem<G, U> a, b;
-  small_fetch<G, U, NT, PR == 0>(A, sp, pb, gw, gl, ipv4, a);
+  small_fetch<G, U, NT, PR == 0>(A, sp, pb, gw, gl, ipv4, dense, a);
   if (PR) run_side(pb, rs);
   for (;;) {
     if (!step(a, b)) break;
@@ -859,12 +937,6 @@ __device__ __forceinline__ void lane_store(const BatchArgs &A, uint64_t pb, uint
     const uint4 c = slice[64 * u + lane];
     __builtin_amdgcn_raw_buffer_store_b128(u32x4{c.x, c.y, c.z, c.w}, r, (int)(off < span ? off : kOOB), 0, 0);
   }
-}
-
-__device__ __forceinline__ void wave_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 template <int U, int NT>
