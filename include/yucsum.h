@@ -19,8 +19,8 @@
  *     total functions (never fail), reentrant and allocation-free.
  *
  *  2. Batched device entry points (yu_csum_batch_uniform,
- *     yu_csum_batch_ragged). These are the GPU hot path: one launch computes
- *     the per-packet sums of a whole device-resident batch with hand-written
+ *     yu_csum_batch_ragged, yu_csum_batch_iov and the yu_csum_fill_* forms).
+ *     These are the GPU hot path: one launch computes the per-packet sums of a whole device-resident batch with hand-written
  *     gfx950 HIP kernels. They are asynchronous on the given HIP stream,
  *     perform no allocation and no synchronisation (graph-capturable), and
  *     return a status code. There is no CPU fallback: without a usable GPU
@@ -66,18 +66,23 @@ extern "C" {
 /* agree. All are checked before any device work; a call that returns  */
 /* YU_EINVAL has read no packet byte and written nothing.               */
 /*                                                                      */
-/*  [mode]          mode is not 0 .. YU_MODE_COUNT-1 (every call).       */
+/*  [mode]          mode is not 0 .. YU_MODE_COUNT-1 (every call); the   */
+/*                  scatter-gather device calls (yu_csum_*_iov): also   */
+/*                  IPV4, VERIFY_IPV4, VERIFY_RX and TX_DATAGRAM, which  */
+/*                  parse headers out of the packet.                     */
 /*  [out]           out == NULL in a yu_csum_batch_* call, or h_out ==   */
 /*                  NULL in a yu_csum_batch_host_* call, with n > 0 (the */
 /*                  fill calls take NULL: no result array; an empty     */
 /*                  batch, n == 0, is a no-op returning YU_OK).          */
 /*  [fill-mode]     a fill call (yu_csum_fill_*) with a mode that has no */
-/*                  field to write: RAW, VERIFY_* (or no mode at all).   */
+/*                  field to write: RAW, VERIFY_* (or no mode at all);   */
+/*                  yu_csum_fill_iov: any mode but UDP, TCP and ICMP.    */
 /*  [side-align]    device calls: initial_arr not 2-byte aligned, addrs  */
 /*                  not 4-byte aligned, out not 2-byte aligned.          */
 /*  [data]          data == NULL with n > 0 (device calls), h_data ==    */
 /*                  NULL while the packets hold bytes (host calls), iov  */
-/*                  == NULL while first_iov names views.                 */
+/*                  == NULL while first_iov names views; views == NULL  */
+/*                  with n > 0 (yu_csum_*_iov).                          */
 /*  [len-transport] a packet of a mode other than RAW longer than        */
 /*                  YU_MAX_TRANSPORT_LEN (uniform len; every host ragged */
 /*                  or iov packet). Device ragged batches are not read   */
@@ -88,7 +93,9 @@ extern "C" {
 /*  [span]          uniform: data + (n-1)*stride + len wraps the address */
 /*                  space.                                               */
 /*  [offsets]       offsets == NULL, or (device) not 8-byte aligned, or  */
-/*                  (host) decreasing; first_iov == NULL or decreasing.  */
+/*                  (host) decreasing; first_iov == NULL or decreasing;  */
+/*                  yu_csum_*_iov (device tables): first_iov == NULL or  */
+/*                  not 8-byte aligned, views not 8-byte aligned.        */
 /*  [iov-view]      a view with base == NULL and len > 0.                */
 /*  [fill-align]    yu_csum_fill_uniform: data or stride not a multiple  */
 /*                  of 4. The uniform writers store whole dwords of each */
@@ -356,6 +363,67 @@ int yu_csum_batch_host_iov(const yu_iovec *iov, const uint64_t *first_iov,
                            uint16_t initial, const uint8_t *h_addrs,
                            uint16_t *h_out, int device);
 
+/* ------------------------------------------------------------------ */
+/* Scatter-gather packets on the device.                               */
+/* ------------------------------------------------------------------ */
+
+/* The reference never holds an outgoing packet as one buffer: sendUDP
+ * (transport/udp/endpoint.go:164-187), sendTCP (transport/tcp/connect.go:
+ * 556-586) and sendICMPv4 (network/ipv4/icmp.go:36-45) build the transport
+ * header in a buffer.Prependable, leave the payload in its own buffer.View and
+ * sum the two separately; received packets are a VectorisedView of up to four
+ * views (link/tundev/tundev.go:116-125). These calls take that layout where it
+ * lies in device memory, without a packed copy: packet i is the concatenation
+ * of views[first_iov[i]] .. views[first_iov[i+1] - 1], the CSR layout and the
+ * yu_iovec of the host form above.
+ *
+ * `views`, `first_iov` (n + 1 entries), every `base`, the side arrays and `out`
+ * are DEVICE pointers. Like the other device calls: asynchronous on `stream`,
+ * no allocation, no synchronisation, graph-capturable, YU_ENODEV without a
+ * device; n == 0 is a no-op returning YU_OK.
+ *
+ * Value: out[i] is exactly what yu_csum_batch_ragged returns for the same
+ * bytes laid back to back, with the same side arguments.
+ *
+ * Modes: the whole-packet sums RAW, UDP, TCP, ICMP, VERIFY_TCP, VERIFY_UDP.
+ * The TX modes take the checksum field as 0 wherever its two bytes lie, in two
+ * different views included. IPV4, VERIFY_IPV4, VERIFY_RX and TX_DATAGRAM parse
+ * headers out of the packet and are refused here with YU_EINVAL ([mode]; a
+ * follow-up). The fill form takes UDP, TCP and ICMP ([fill-mode]).
+ *
+ * Views: any base address, any length (odd ones included), any number per
+ * packet (0 included), in any address order, in any number of allocations. A
+ * view with len == 0 may have any base, NULL included, and is skipped. The
+ * read-only call may name the same view in many packets (a shared header
+ * template, a shared payload). In a fill call the bytes that hold a field must
+ * belong to one packet only; otherwise those field bytes, and nothing else,
+ * are unspecified.
+ *
+ * Length: a packet's views total at most YU_MAX_TRANSPORT_LEN bytes in every
+ * mode of this form, RAW included.
+ *
+ * Out of contract (the tables are device memory and are not read on the host;
+ * compare "Out of contract" above): a packet whose views total more than the
+ * limit, or at which first_iov decreases. It gets an unspecified value and no
+ * field store, never a fault or a hang: the kernel stops adding view bytes at
+ * the limit. Every other packet's value and field are exact. A call reads only
+ * the dwords that hold the bytes of the views it names and writes, besides
+ * out, only the two field bytes of in-contract packets: as one 16-bit store when both lie in one
+ * view at an even address, as two byte stores otherwise. Pointers are trusted,
+ * as `data` is in the other device calls.
+ *
+ * YU_EINVAL (Preconditions above): [mode], [out], [fill-mode], [side-align];
+ * [data]: views == NULL with n > 0; [offsets]: first_iov == NULL or not 8-byte
+ * aligned, or views not 8-byte aligned. */
+int yu_csum_batch_iov(const yu_iovec *views, const uint64_t *first_iov,
+                      uint64_t n, int mode, const uint16_t *initial_arr,
+                      uint16_t initial, const uint8_t *addrs, uint16_t *out,
+                      void *stream);
+int yu_csum_fill_iov(const yu_iovec *views, const uint64_t *first_iov,
+                     uint64_t n, int mode, const uint16_t *initial_arr,
+                     uint16_t initial, const uint8_t *addrs, uint16_t *out,
+                     void *stream);
+
 /* Host-memory field writer: the matching yu_csum_batch_host_* call (TX modes
  * UDP/TCP/IPV4/ICMP/TX_DATAGRAM only), then each result stored big-endian into the
  * packet's checksum field in host memory, as the device writer does
@@ -483,6 +551,10 @@ const char *yu_ragged_variant_n(int mode, uint64_t n);
 /* The kernel variant yu_csum_fill_ragged launches for a batch of n packets (the
  * TX modes write in place through their own k_seg form). */
 const char *yu_ragged_fill_variant_n(int mode, uint64_t n);
+/* The kernel variant the scatter-gather device calls launch for a batch of n
+ * packets (fill != 0: yu_csum_fill_iov); "" for a mode the form refuses. No
+ * device needed. */
+const char *yu_iov_variant_n(int mode, uint64_t n, int fill);
 
 #ifdef __cplusplus
 }

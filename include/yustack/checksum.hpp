@@ -259,6 +259,27 @@ inline void FillRagged(uint8_t *data, const uint64_t *offsets, uint64_t n, Mode 
   if (rc) throw Error(rc, "yu_csum_fill_ragged");
 }
 
+// Scatter-gather packets where they lie in device memory (a header pool and a
+// payload pool, a VectorisedView): packet i = views[first_iov[i]] ..
+// views[first_iov[i+1] - 1], every pointer a DEVICE pointer, the tables included.
+// Whole-packet modes only (RAW, UDP, TCP, ICMP, VERIFY_TCP, VERIFY_UDP; FillIov:
+// UDP, TCP, ICMP), packets of at most YU_MAX_TRANSPORT_LEN bytes; each result is
+// what Ragged gives for the same bytes laid back to back. FillIov stores the
+// field through the views, across two of them if need be.
+inline void BatchIov(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, Mode m,
+                     uint16_t *out, const Side &s = {}, void *stream = nullptr) {
+  int rc = yu_csum_batch_iov(views, first_iov, n, m, s.initial_arr, s.initial, s.addrs, out,
+                             stream);
+  if (rc) throw Error(rc, "yu_csum_batch_iov");
+}
+
+inline void FillIov(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, Mode m,
+                    uint16_t *out = nullptr, const Side &s = {}, void *stream = nullptr) {
+  int rc = yu_csum_fill_iov(views, first_iov, n, m, s.initial_arr, s.initial, s.addrs, out,
+                            stream);
+  if (rc) throw Error(rc, "yu_csum_fill_iov");
+}
+
 // Host buffers in, host results out (pinned staging + pipelined copies, or
 // the direct path for bursts up to 4 MiB). Here `Side` holds HOST pointers.
 // A device list shards the batch over several GPUs (the *_multi calls).

@@ -16,13 +16,13 @@ LIB_PATH = os.path.join(HERE, "libyucsum.so")
 EXPORTS = (
     "yu_checksum", "yu_checksum_combine", "yu_pseudo_header_checksum",
     "yu_csum_batch_uniform", "yu_csum_batch_ragged",
-    "yu_csum_fill_uniform", "yu_csum_fill_ragged",
+    "yu_csum_fill_uniform", "yu_csum_fill_ragged", "yu_csum_batch_iov", "yu_csum_fill_iov",
     "yu_csum_batch_host_uniform", "yu_csum_batch_host_ragged", "yu_csum_batch_host_iov",
     "yu_csum_batch_host_uniform_multi", "yu_csum_batch_host_ragged_multi",
     "yu_csum_batch_host_iov_multi",
     "yu_csum_fill_host_uniform", "yu_csum_fill_host_ragged", "yu_csum_fill_host_iov",
     "yu_abi_version", "yu_strerror", "yu_device_count", "yu_uniform_variant", "yu_uniform_variant_n",
-    "yu_ragged_variant", "yu_ragged_variant_n", "yu_ragged_fill_variant_n",
+    "yu_ragged_variant", "yu_ragged_variant_n", "yu_ragged_fill_variant_n", "yu_iov_variant_n",
     "yu_host_contexts", "yu_host_staging_bytes", "yu_host_staging_trim", "yu_hip_runtime_path",
 )
 
@@ -86,7 +86,7 @@ def lib() -> ctypes.CDLL:
         f = getattr(L, name)
         f.restype = i32
         f.argtypes = [vp, u64, u32, u64, i32, vp, u16, vp, vp, vp]
-    for name in ("yu_csum_batch_ragged", "yu_csum_fill_ragged"):
+    for name in ("yu_csum_batch_ragged", "yu_csum_fill_ragged", "yu_csum_batch_iov", "yu_csum_fill_iov"):
         f = getattr(L, name)
         f.restype = i32
         f.argtypes = [vp, vp, u64, i32, vp, u16, vp, vp, vp]
@@ -124,6 +124,8 @@ def lib() -> ctypes.CDLL:
     L.yu_ragged_variant_n.argtypes = [i32, u64]
     L.yu_ragged_fill_variant_n.restype = c.c_char_p
     L.yu_ragged_fill_variant_n.argtypes = [i32, u64]
+    L.yu_iov_variant_n.restype = c.c_char_p
+    L.yu_iov_variant_n.argtypes = [i32, u64, i32]
     L.yu_host_contexts.restype = i32
     L.yu_host_contexts.argtypes = []
     L.yu_host_staging_bytes.restype = u64

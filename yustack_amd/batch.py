@@ -1,8 +1,8 @@
 """Batched Internet checksum on MI355X — the hot path.
 
 Thin Python front end over the C ABI's batched entry points
-(``yu_csum_batch_uniform`` / ``yu_csum_batch_ragged`` / ``yu_csum_fill_*`` /
-``yu_csum_batch_host_uniform``, include/yucsum.h). PyTorch is used only for device
+(``yu_csum_batch_uniform`` / ``yu_csum_batch_ragged`` / ``yu_csum_batch_iov`` /
+``yu_csum_fill_*`` / ``yu_csum_batch_host_uniform``, include/yucsum.h). PyTorch is used only for device
 memory and streams: the arithmetic happens in the hand-written gfx950 kernels of
 ``csrc/yucsum_kernels.hip``. There is no CPU fallback — without a HIP device every
 entry point raises :class:`yustack_amd._lib.YuError`.
@@ -153,6 +153,113 @@ def checksum_ragged(data: torch.Tensor, offsets: torch.Tensor, mode="raw", *, in
                _ptr(addrs), out.data_ptr() if n else None, _stream(dev, stream))
     check(rc, "yu_csum_fill_ragged" if fill else "yu_csum_batch_ragged")
     return out
+
+
+IOV_MODES = (RAW, UDP, TCP, ICMP, VERIFY_TCP, VERIFY_UDP)
+IOV_FILL_MODES = (UDP, TCP, ICMP)
+
+
+def _dev_index(t, name: str, device, numel: int | None = None) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
+        raise TypeError(f"{name} must be a CUDA tensor on {device}")
+    if t.dtype not in (torch.int32, torch.int64, torch.uint64) or t.dim() != 1:
+        raise TypeError(f"{name} must be a 1-D int32/int64/uint64 tensor")
+    if numel is not None and t.numel() != numel:
+        raise ValueError(f"{name} must hold {numel} entries")
+    return (t.view(torch.int64) if t.dtype == torch.uint64 else t.to(torch.int64)).contiguous()
+
+
+def checksum_iov(pools, view_pool: torch.Tensor, view_off: torch.Tensor, view_len: torch.Tensor,
+                 first: torch.Tensor, mode="raw", *, initial: int = 0,
+                 initial_arr: torch.Tensor | None = None, addrs: torch.Tensor | None = None,
+                 out: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None,
+                 fill: bool = False, validate: bool = True) -> torch.Tensor:
+    """Per-packet sums of scatter-gather device packets (yu_csum_batch_iov /
+    yu_csum_fill_iov): view j is ``pools[view_pool[j]][view_off[j] : view_off[j] + view_len[j]]``
+    and packet i the concatenation of views ``first[i] .. first[i+1]-1`` (``first``: n+1
+    non-decreasing entries), e.g. a header pool and a payload pool. ``pools`` is a
+    list of contiguous uint8 CUDA tensors on one device; the view arrays and
+    ``first`` are CUDA integer tensors there. Each result is what
+    :func:`checksum_ragged` gives for the same bytes laid back to back. Modes: RAW,
+    UDP, TCP, ICMP, VERIFY_TCP, VERIFY_UDP; packets of at most 65535 bytes.
+    ``fill=True`` (UDP, TCP, ICMP) also stores each result big-endian into the
+    packet's checksum field where it lies in the pools, across two views if need be.
+
+    The device ``yu_iovec`` table is built with torch operations (no host loop
+    over views; capturable in a graph with ``validate=False``). ``validate`` checks
+    on the device that every view lies inside its pool, that ``first`` is
+    non-decreasing within the view count and that no packet is longer than 65535
+    bytes (one small synchronisation). The returned tensor holds the table
+    (``out.iov_table``), which must outlive the enqueued call."""
+    m = _mode(mode)
+    if m not in IOV_MODES:
+        raise ValueError("checksum_iov takes the whole-packet modes: raw, udp, tcp, icmp, verify_tcp, verify_udp")
+    if fill and m not in IOV_FILL_MODES:
+        raise ValueError("fill=True takes udp, tcp or icmp")
+    pools = list(pools)
+    if not pools:
+        raise ValueError("pools must hold at least one tensor")
+    for k, pool in enumerate(pools):
+        _dev_u8(pool, f"pools[{k}]")
+    dev = pools[0].device
+    if any(pool.device != dev for pool in pools):
+        raise TypeError("pools must be on one device")
+    vp = _dev_index(view_pool, "view_pool", dev)
+    nviews = vp.numel()
+    vo = _dev_index(view_off, "view_off", dev, nviews)
+    vl = _dev_index(view_len, "view_len", dev, nviews)
+    fi = _dev_index(first, "first", dev)
+    n = fi.numel() - 1
+    if n < 0:
+        raise ValueError("first must hold n+1 entries")
+    # base = pools[k].data_ptr() + off: one pass per pool, none per view
+    base = torch.zeros_like(vo)
+    size = torch.zeros_like(vo)
+    for k, pool in enumerate(pools):
+        sel = vp == k
+        base = torch.where(sel, vo + pool.data_ptr(), base)
+        size = torch.where(sel, torch.full_like(vo, pool.numel()), size)
+    if validate and n > 0:
+        ends = torch.zeros(nviews + 1, dtype=torch.int64, device=dev)
+        ends[1:] = torch.cumsum(vl.clamp(min=0), 0)
+        ok_first = (fi[1:] >= fi[:-1]).all() & (fi[0] >= 0) & (fi[-1] <= nviews)
+        ok_view = ((vp >= 0) & (vp < len(pools)) & (vo >= 0) & (vl >= 0) & (vl <= size) &
+                   (vo <= size - vl)).all()
+        f = fi.clamp(0, nviews)
+        ok_len = ((ends[f[1:]] - ends[f[:-1]]) <= MAX_TRANSPORT_LEN).all()
+        okf, okv, okl = torch.stack((ok_first, ok_view, ok_len)).tolist()
+        if not okf:
+            raise ValueError("first is not non-decreasing within the view count")
+        if not okv:
+            raise ValueError("a view does not lie inside its pool")
+        if not okl:
+            raise ValueError("scatter-gather packets must be <= 65535 bytes")
+    table = torch.stack((base, vl), dim=1).contiguous() if nviews else \
+        torch.zeros((1, 2), dtype=torch.int64, device=dev)
+    initial_arr = _opt(initial_arr, torch.uint16, n, dev, "initial_arr")
+    addrs = _opt(addrs, torch.uint8, 8 * n, dev, "addrs")
+    if out is None:
+        out = torch.empty(max(n, 1), dtype=torch.uint16, device=dev)[:n]
+    else:
+        _opt(out, torch.uint16, n, dev, "out")
+    if stream is not None:  # the table was built on the current stream
+        stream.wait_stream(torch.cuda.current_stream(dev))
+        table.record_stream(stream)
+        fi.record_stream(stream)
+    with torch.cuda.device(dev):
+        name = "yu_csum_fill_iov" if fill else "yu_csum_batch_iov"
+        rc = getattr(lib(), name)(table.data_ptr(), fi.data_ptr(), n, m, _ptr(initial_arr),
+                                  initial & 0xFFFF, _ptr(addrs), out.data_ptr() if n else None,
+                                  _stream(dev, stream))
+    check(rc, name)
+    out.iov_table = (table, fi)
+    return out
+
+
+def iov_variant(mode="raw", n: int = 1 << 20, fill: bool = False) -> str:
+    """Name of the kernel the scatter-gather device calls launch ("" for a mode
+    they refuse)."""
+    return lib().yu_iov_variant_n(_mode(mode), n, 1 if fill else 0).decode()
 
 
 def _host_data(data, fill: bool):

@@ -70,6 +70,9 @@
 //     and ragged: one lane per packet, 32-byte reads.
 //   k_loop<U, BE> / k_loop_rx<U>: one wave per packet, for ragged bursts of up
 //     to 4096 packets and for few or sparse uniform packets > 4 KiB.
+//   k_iov<U, NT, FILL>: scatter-gather packets (yu_csum_batch_iov / yu_csum_fill_iov,
+//     planned by yu::plan_iov): one wave per packet walking its views, each step U
+//     load slots of 1 KiB of whichever view comes next (yucsum_iov.h).
 //   All are grid-stride kernels; the grid is sized per CU and over-subscribed
 //   (see blocks_per_cu in yucsum_plan.cpp), except that k_seg narrows it for
 //   small packets (seg_waves).
@@ -83,6 +86,7 @@
 #include "yucsum.h"
 #include "yucsum_dense.h"
 #include "yucsum_internal.h"
+#include "yucsum_iov.h"
 #include "yucsum_plan.h"
 
 namespace {
@@ -2174,6 +2178,255 @@ __global__ __launch_bounds__(256) void k_loop_rx(BatchArgs A) {
 }
 
 // ---------------------------------------------------------------------
+// k_iov<U, NT, FILL>: scatter-gather packets (yu_csum_batch_iov /
+// yu_csum_fill_iov), one wave per packet. The arithmetic, the walk over a
+// packet's views and the load slots it cuts them into are yucsum_iov.h's; a
+// step here is U slots, so a 2-view MTU packet (header view, payload view) is
+// one step. The loads of the next step (of this packet or the next) are issued
+// before the current one is summed, and everything a packet needs besides its
+// bytes is fetched ahead of the walk: first_iov two packets ahead with scalar
+// loads, issued at one point per packet (scalar loads return out of order, so
+// using one waits for all of them); the packet's first 64 view records, one
+// per lane, and its side data, by the lead lane, one packet ahead, with loads
+// whose idle lanes pass kOOB. The walk reads a record with v_readlane; only
+// views past a packet's 64th are read as the walk reaches them. first_iov and
+// those late records go through constant-address-space pointers, which is what
+// makes a uniform load a scalar one whatever the kernel stores: no store of a
+// call (out, the fields) may touch the tables.
+// NT: 0 plain loads, 1 nt, 2 plain for a step's first slot (a short header
+// view, whose line its neighbours share) and nt for the rest.
+// ---------------------------------------------------------------------
+#define YU_CONST_AS __attribute__((address_space(4)))
+template <typename T>
+__device__ __forceinline__ const YU_CONST_AS T *const_as(const T *p) {
+  return (const YU_CONST_AS T *)(uintptr_t)p;
+}
+
+struct IovArgs {
+  uint16_t *out;
+  uint64_t n;
+  uint32_t initial;
+  int mode;
+};
+
+// A packet's place in the view table and its first 64 view records, one per
+// lane (lanes past the packet's views hold an empty view).
+struct IovPkt {
+  uint64_t g0;      // index of the packet's first view
+  uint32_t nv;      // its views (0 when first_iov decreases: out of contract)
+  uint32_t blo, bhi, len;  // lane k: view g0 + k (a length past 32 bits is past every limit: clamped)
+  uint32_t sa, sb, si;     // lead lane: the {src, dst} record; initial_arr's entry or the scalar initial
+};
+
+// What finishing a packet needs, taken when the walk leaves it. Only the lead
+// lane uses it, so but for `last` it lives in that lane's vector registers.
+struct IovFin {
+  bool last;     // the step is its packet's last (wave-uniform)
+  uint32_t len;  // the packet's bytes; bit 31: out of contract, no field store
+  uint64_t fp0, fp1;
+  uint32_t sa, sb, si;
+};
+
+template <int U, int NT, bool FILL>
+__global__ __launch_bounds__(256) void k_iov(const yu_iovec *views_, const uint64_t *first_,
+                                             const uint16_t *initial_arr, const uint8_t *addrs_,
+                                             IovArgs A) {
+  const YU_CONST_AS yu_iovec *views = const_as(views_);
+  const YU_CONST_AS uint64_t *first = const_as(first_);
+  const uint32_t lane = threadIdx.x & 63u;
+  const bool lead = lane == 63;
+  const uint64_t wave = grid_wave(0u);
+  const uint64_t nwave = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  const int mode = A.mode;
+  const uint32_t f = yu::iov_mode_field(mode);
+  const bool tx = f != 0;  // == yu::iov_mode_tx(mode)
+  const uint8_t *addrs = mode_has_pseudo(mode) ? addrs_ : nullptr;
+  if (wave >= A.n) return;
+
+  // first_iov[q], first_iov[q + 1] of packet q (none: an empty packet)
+  auto first_pair = [&](uint64_t q, uint64_t &f0, uint64_t &f1) __attribute__((always_inline)) {
+    f0 = f1 = 0;
+    if (q < A.n) {
+      f0 = first[q];
+      f1 = first[q + 1];
+    }
+  };
+  // The packet with views [f0, f1): lane k loads record f0 + k, lanes past the
+  // packet's views (and past 64 of them) nothing.
+  auto packet = [&](IovPkt &P, uint64_t q, uint64_t f0, uint64_t f1) __attribute__((always_inline)) {
+    const uint64_t nv = f1 >= f0 ? f1 - f0 : 0;
+    P.g0 = f0;
+    P.nv = nv < 0xFFFFFFFFull ? (uint32_t)nv : 0xFFFFFFFFu;
+    const uint64_t base = uniform64((uint64_t)(uintptr_t)(views_ + f0));
+    const __amdgpu_buffer_rsrc_t r = rsrc_at(base, base + 16u * (P.nv < 64u ? P.nv : 64u));
+    const uint4 v = bld16(r, 16u * lane, false);
+    P.blo = v.x;
+    P.bhi = v.y;
+    P.len = v.w ? 0xFFFFFFFFu : v.z;
+    // the packet's side data, by the lead lane alone (an absent array: nothing)
+    const uint32_t own = lead && q < A.n ? 0u : kOOB;
+    const uint64_t ab = uniform64(addrs ? (uint64_t)(uintptr_t)(addrs + 8 * q) : 0ull);
+    const uint64_t ib = uniform64(initial_arr ? (uint64_t)(uintptr_t)(initial_arr + q) : 0ull);
+    const __amdgpu_buffer_rsrc_t ra =
+        __builtin_amdgcn_make_buffer_rsrc((void *)ab, (short)0, addrs ? 8 : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ri =
+        __builtin_amdgcn_make_buffer_rsrc((void *)ib, (short)0, initial_arr ? 2 : 0, 0x00020000);
+    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+    const u32x2 sab = __builtin_amdgcn_raw_buffer_load_b64(ra, (int)own, 0, 0);
+    const uint16_t sin = __builtin_amdgcn_raw_buffer_load_b16(ri, (int)own, 0, 0);
+    P.sa = sab.x;
+    P.sb = sab.y;
+    P.si = initial_arr ? (uint32_t)sin : A.initial;
+  };
+
+  // The walk: packet wp, view vi of it; nx: packet wp + nwave; (ff0, ff1):
+  // first_iov of packet wp + 2 nwave.
+  uint64_t wp = wave, ff0, ff1;
+  IovPkt cur, nx;
+  {
+    uint64_t a0, a1, b0, b1;
+    first_pair(wp, a0, a1);
+    first_pair(wp + nwave, b0, b1);
+    first_pair(wp + 2 * nwave, ff0, ff1);
+    packet(cur, wp, a0, a1);
+    packet(nx, wp + nwave, b0, b1);
+  }
+  yu::IovWalk W;
+  yu::iov_walk_reset(W);
+  uint32_t vi = 0;
+
+  // Makes the walk's current view one with bytes left, if the packet has one.
+  auto next_view = [&]() __attribute__((always_inline)) {
+    while (yu::iov_walk_done(W) && vi < cur.nv) {
+      uint64_t b;
+      uint32_t l;
+      if (vi < 64u) {
+        b = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)cur.bhi, (int)vi) << 32) |
+            (uint32_t)__builtin_amdgcn_readlane((int)cur.blo, (int)vi);
+        l = (uint32_t)__builtin_amdgcn_readlane((int)cur.len, (int)vi);
+      } else {  // past the records the lanes hold: read as the walk gets there
+        const uint64_t vl = views[cur.g0 + vi].len;
+        b = (uint64_t)(uintptr_t)views[cur.g0 + vi].base;
+        l = vl < 0xFFFFFFFFull ? (uint32_t)vl : 0xFFFFFFFFu;
+      }
+      yu::iov_walk_view(W, b, l, tx, f);
+      ++vi;
+    }
+  };
+  // The walk's next step: its slots' info words, their loads issued into c, and
+  // what finishing needs when the step is its packet's last (the walk then
+  // moves on to the next packet).
+  auto produce = [&](uint32_t (&info)[U], uint4 (&c)[U], IovFin &fin) __attribute__((always_inline)) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      next_view();
+      yu::IovSlot S;
+      yu::iov_walk_slot(W, S);
+      info[u] = S.info;
+      const uint32_t lim = yu::iov_lim(S.info);
+      const uint64_t base = uniform64(S.base);
+      const __amdgpu_buffer_rsrc_t r = rsrc_at(base, base + lim);
+      const uint32_t cr = 16u * lane;
+      c[u] = bld16(r, cr < lim ? cr : kOOB, NT == 1 || (NT == 2 && u != 0));
+    }
+    next_view();
+    fin.last = yu::iov_walk_done(W) && vi >= cur.nv;
+    if (fin.last) {
+      fin.len = lead ? (W.off | (W.over << 31)) : 0u;
+      fin.fp0 = lead ? W.fp[0] : 0ull;
+      fin.fp1 = lead ? W.fp[1] : 0ull;
+      fin.sa = cur.sa;
+      fin.sb = cur.sb;
+      fin.si = cur.si;
+      wp += nwave;
+      cur = nx;
+      packet(nx, wp + nwave, ff0, ff1);
+      first_pair(wp + 2 * nwave, ff0, ff1);
+      yu::iov_walk_reset(W);
+      vi = 0;
+    }
+  };
+
+  uint64_t p = wave;  // the packet being summed
+  uint32_t accA = 0, accB = 0;  // per lane: LE sums of the swapped / unswapped class
+  uint32_t jA = 0, jB = 0;      // the field bytes' share of them (kept by the lead lane)
+  // One step: issue the walk's next step into (in, cn, fn), then sum (ic, c) and
+  // finish its packet if it ends one. false: the wave's last packet is done. The
+  // loop alternates two sets of registers instead of copying (see k_small).
+  auto step = [&](uint32_t (&ic)[U], uint4 (&c)[U], IovFin &fc, uint32_t (&in)[U], uint4 (&cn)[U],
+                  IovFin &fn) __attribute__((always_inline)) -> bool {
+    produce(in, cn, fn);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint32_t info = ic[u];
+      const uint32_t lim = yu::iov_lim(info);
+      if (lim == 0) continue;  // an empty slot (wave-uniform): zeros came back
+      uint32_t t = 0;
+      if (lim >= yu::kIovSlot && !(info & yu::kIovFirst)) {
+        t = sum_full<false>(c[u], 0u, 0u);
+      } else {
+        const uint32_t hm = yu::iov_head_mask(info);
+        const uint32_t cr = 16u * lane;
+        t = yu::iov_add(yu::iov_dword(c[u].x, cr, lim, hm), t);
+        t = yu::iov_add(yu::iov_dword(c[u].y, cr + 4u, lim, hm), t);
+        t = yu::iov_add(yu::iov_dword(c[u].z, cr + 8u, lim, hm), t);
+        t = yu::iov_add(yu::iov_dword(c[u].w, cr + 12u, lim, hm), t);
+      }
+      const bool swap = (info & yu::kIovSwap) != 0;
+      if (info & (yu::kIovF0 | yu::kIovF1)) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          if (yu::iov_has_field(info, k)) {
+            const uint32_t q = yu::iov_field_q(info, k);
+            const uint32_t word = (uint32_t)__builtin_amdgcn_readlane(
+                (int)pick_dword(c[u], (q >> 2) & 3u), (int)(q >> 4));
+            const uint32_t term = yu::iov_field_term(word, q);
+            jA += (lead && swap) ? term : 0u;
+            jB += (lead && !swap) ? term : 0u;
+          }
+        }
+      }
+      accA += swap ? t : 0u;
+      accB += swap ? 0u : t;
+    }
+    if (!fc.last) return true;
+    uint32_t sA = group_total<64>(accA), sB = group_total<64>(accB);
+    if (lead) {
+      const uint32_t len = fc.len & 0x7FFFFFFFu;
+      const bool fld = tx && len >= f + 2u;  // the whole field lies in the packet
+      if (fld) {
+        sA -= jA;
+        sB -= jB;
+      }
+      const uint32_t r = yu::iov_value(mode, yu::iov_residue(sA, sB), len, addrs != nullptr, fc.sa,
+                                       fc.sb, fc.si);
+      if (A.out) A.out[p] = (uint16_t)r;
+      if (FILL && fld && !(fc.len >> 31)) {  // binary.BigEndian.PutUint16 through the views
+        uint8_t *q0 = (uint8_t *)(uintptr_t)fc.fp0, *q1 = (uint8_t *)(uintptr_t)fc.fp1;
+        if (q1 == q0 + 1 && ((uintptr_t)q0 & 1u) == 0) {
+          *(uint16_t *)q0 = (uint16_t)(((r >> 8) | (r << 8)) & 0xFFFFu);
+        } else {
+          *q0 = (uint8_t)(r >> 8);
+          *q1 = (uint8_t)r;
+        }
+      }
+    }
+    accA = accB = jA = jB = 0;
+    p += nwave;
+    return p < A.n;
+  };
+
+  uint32_t i0[U], i1[U];
+  uint4 c0[U], c1[U];
+  IovFin n0, n1;
+  produce(i0, c0, n0);
+  for (;;) {
+    if (!step(i0, c0, n0, i1, c1, n1)) break;
+    if (!step(i1, c1, n1, i0, c0, n0)) break;
+  }
+}
+
+// ---------------------------------------------------------------------
 // Host side: launch. Which kernel, form, load policy and grid a batch gets is
 // yu::plan's decision (yucsum_plan.cpp); here are the functions it names.
 // ---------------------------------------------------------------------
@@ -2335,6 +2588,41 @@ int batch_ragged(const uint8_t *data, uint8_t *fill, const uint64_t *offsets,
   return launch({true, 0, 0, 0, n, mode, fill != nullptr}, A, (hipStream_t)stream);
 }
 
+typedef void (*IovFn)(const yu_iovec *, const uint64_t *, const uint16_t *, const uint8_t *, IovArgs);
+const IovFn kIovFns[yu::kIovKernelCount][3] = {
+    {k_iov<4, 0, false>, k_iov<4, 1, false>, k_iov<4, 2, false>},
+    {k_iov<4, 0, true>, k_iov<4, 1, true>, k_iov<4, 2, true>},
+};
+
+// The scatter-gather device calls. The tables are device memory and are not
+// read here (include/yucsum.h, "Out of contract").
+int batch_iov(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode,
+              const uint16_t *initial_arr, uint16_t initial, const uint8_t *addrs, uint16_t *out,
+              bool fill, void *stream) {
+  if (mode < 0 || mode >= YU_MODE_COUNT) return YU_EINVAL;     // EINVAL:mode
+  if (fill && !yu::iov_mode_tx(mode)) return YU_EINVAL;         // EINVAL:fill-mode (no field, or a mode this form refuses)
+  if (!yu::iov_mode_ok(mode)) return YU_EINVAL;                 // EINVAL:mode (IPV4, VERIFY_IPV4, VERIFY_RX, TX_DATAGRAM parse headers)
+  if (!out && !fill && n) return YU_EINVAL;                     // EINVAL:out
+  if (initial_arr && !aligned(initial_arr, 2)) return YU_EINVAL;  // EINVAL:side-align
+  if (addrs && !aligned(addrs, 4)) return YU_EINVAL;              // EINVAL:side-align
+  if (out && !aligned(out, 2)) return YU_EINVAL;                  // EINVAL:side-align
+  if (n == 0) return YU_OK;
+  if (!first_iov || !aligned(first_iov, 8) || !aligned(views, 8)) return YU_EINVAL;  // EINVAL:offsets
+  if (!views) return YU_EINVAL;                                                     // EINVAL:data
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return hip_status(e);
+  const yu::IovPlan p = yu::plan_iov(n, mode, fill, cu_count(dev), yu::env_knobs());
+  IovArgs a;
+  a.out = out;
+  a.n = n;
+  a.initial = initial;
+  a.mode = mode;
+  hipLaunchKernelGGL(kIovFns[p.kernel][p.policy], dim3(p.blocks), dim3(256), 0, (hipStream_t)stream,
+                     views, first_iov, initial_arr, addrs, a);
+  return hip_status(hipGetLastError());
+}
+
 // Completion signal for the host path's direct mode (yucsum_internal.h):
 // stored after the work before it on the stream, with system-scope release,
 // into coherent pinned host memory.
@@ -2387,6 +2675,24 @@ int yu_csum_fill_ragged(uint8_t *data, const uint64_t *offsets, uint64_t n,
   // write-back stores only 128-byte lines that lie inside its own chunk's packets.
   return batch_ragged(data, data, offsets, n, mode, initial_arr, initial,
                       addrs, out, stream);
+}
+
+int yu_csum_batch_iov(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode,
+                      const uint16_t *initial_arr, uint16_t initial, const uint8_t *addrs,
+                      uint16_t *out, void *stream) {
+  return batch_iov(views, first_iov, n, mode, initial_arr, initial, addrs, out, false, stream);
+}
+
+int yu_csum_fill_iov(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode,
+                     const uint16_t *initial_arr, uint16_t initial, const uint8_t *addrs,
+                     uint16_t *out, void *stream) {
+  return batch_iov(views, first_iov, n, mode, initial_arr, initial, addrs, out, true, stream);
+}
+
+const char *yu_iov_variant_n(int mode, uint64_t n, int fill) {
+  if (mode < 0 || mode >= YU_MODE_COUNT || !yu::iov_mode_ok(mode)) return "";
+  if (fill && !yu::iov_mode_tx(mode)) return "";
+  return yu::plan_iov(n, mode, fill != 0, 256, yu::env_knobs()).name;
 }
 
 const char *yu_uniform_variant(uint64_t stride, uint32_t len, int mode,

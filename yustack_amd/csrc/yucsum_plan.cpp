@@ -282,4 +282,22 @@ Plan plan(const Shape &s, int cus, const Knobs &k) {
   return p;
 }
 
+// k_iov: a wave per packet on the over-subscribed grid of the other
+// wave-per-packet kernels (64 blocks per CU, YU_BLOCKS_PER_CU overrides); the
+// load policy is YU_NT's, else slot 2. `mode` does not enter yet: every mode the
+// form takes is a whole-packet sum on the same kernel.
+IovPlan plan_iov(uint64_t n, int mode, bool fill, int cus, const Knobs &k) {
+  (void)mode;
+  IovPlan p;
+  p.kernel = fill ? k_iov4_fill : k_iov4;
+  p.name = fill ? "k_iov<4,fill>" : "k_iov<4>";
+  p.policy = (uint8_t)(k.nt >= 0 ? k.nt : 2);
+  const uint64_t cap = (uint64_t)cus * (k.blocks_per_cu ? k.blocks_per_cu : 64u);
+  uint64_t blocks = (n + 3) / 4;  // 4 waves per block, a wave per packet
+  if (blocks > cap) blocks = cap;
+  if (blocks < 1) blocks = 1;
+  p.blocks = (uint32_t)blocks;
+  return p;
+}
+
 }  // namespace yu
