@@ -8,10 +8,21 @@ tests/ledger_child.py runs the cases of one knob set on the GPU;
 tests/test_gpu_kernel_ledger.py starts one child per knob set.
 
 A case is a dict:
-  id        its position in CASES and a short description
+  id        its position in CASES and a short description (cases are only appended: the
+            child seeds a case's bytes from its position)
   layout    "U" (uniform: stride, len, base = the first packet's offset in a 128-byte
-            aligned buffer) or "R" (ragged: gen = (name, lo, hi), base)
-  mode, fill, side ("scalar" | "init" | "addrs"), kind ("rand" | "zero" | "ff")
+            aligned buffer), "R" (ragged: gen = (name, lo, hi), base) or "I" (scatter-gather,
+            k_iov: iov = the view shape, iov_packets)
+  mode, fill, side ("scalar" | "init" | "addrs")
+  kind      "rand" | "zero" | "ff" (constant bytes), or a zero pole: "pole_side"
+            (initial_arr solved so that every packet sums to its pole) or "pole_data" (the
+            16-bit word at POLE_W solved instead); the pole is 0x0000 for UDP, TCP, ICMP and
+            IPV4, 0xFFFF for RAW and the VERIFY modes (pole)
+  call      how the call is made: "plain" (through batch.py, fresh aligned arrays), or the
+            C ABI itself with any of "offset" (out, initial_arr, addrs, offsets and the
+            scatter-gather tables at the least alignment include/yucsum.h allows),
+            "null_out" (in place, out = NULL) and "ignored" (junk in the arguments the mode
+            does not use: ignores), joined by "+"
   n         the packet count, or "n_wrap": the smallest n above one pass of the grid
             (resolve_n), kept within [n_lo, n_hi], the planner's count cut-overs
   ppw       packets per wave the plan is expected to have (n_wrap needs it)
@@ -79,17 +90,29 @@ def _policy(s, fill, fill_plain):
     return int(nt) if nt is not None else (0 if fill and fill_plain else 2)
 
 
+def kernel_of(c):
+    """(kernel, form) of a case: the same under every set it runs in."""
+    return tuple(next(iter(c["plans"].values())).split()[:2])
+
+
+def _append(c):
+    """Gives the case its id (its position in CASES and what it is) and appends it."""
+    kernel, form = kernel_of(c)
+    g = (f"{c['len']}/{c['stride']}@{c['base']}" if c["layout"] == "U" else c["iov"] if c["layout"] == "I" else
+         "%s[%d..%d]@%d" % (*c["gen"], c["base"]))
+    c["id"] = (f"{len(CASES):04d} {kernel} {form} {c['layout']} {c['mode']}{' fill' if c['fill'] else ''} {g} "
+               f"n={c['n']} {c['side']} {c['kind']}{'' if c['call'] == 'plain' else ' ' + c['call']}")
+    CASES.append(c)
+
+
 def _add(layout, kernel, form, mode, sets, n, ppw, *, fill=False, fill_plain=False, side=None, kind="rand",
-         n_lo=1, n_hi=None, **geom):
+         n_lo=1, n_hi=None, call="plain", **geom):
     if side is None:  # rotate through what the mode takes
         allowed = SIDES.get(mode, ("scalar",))
         side = allowed[len(CASES) % len(allowed)]
     assert side in SIDES.get(mode, ("scalar",)), (mode, side)
-    c = dict(layout=layout, mode=mode, fill=fill, side=side, kind=kind, n=n, n_lo=n_lo, n_hi=n_hi, ppw=ppw,
-             plans={s: f"{kernel} {form} {_policy(s, fill, fill_plain)}" for s in sets}, **geom)
-    g = f"{geom['len']}/{geom['stride']}@{geom['base']}" if layout == "U" else "%s[%d..%d]@%d" % (*geom["gen"], geom["base"])
-    c["id"] = f"{len(CASES):04d} {kernel} {form} {layout} {mode}{' fill' if fill else ''} {g} n={n} {side} {kind}"
-    CASES.append(c)
+    _append(dict(layout=layout, mode=mode, fill=fill, side=side, kind=kind, n=n, n_lo=n_lo, n_hi=n_hi, ppw=ppw,
+                 call=call, plans={s: f"{kernel} {form} {_policy(s, fill, fill_plain)}" for s in sets}, **geom))
 
 
 def U(kernel, form, mode, length, stride, sets, n, ppw, base=0, **kw):
@@ -374,6 +397,145 @@ for _kern, _ms, _f, _p, _ns, _lo, _hi, _trs in _RSEG:
       side="addrs" if _ms[1] in SIDES else None)
 
 
+# ---------------------------------------------------------------------------
+# Everything above is the ledger as it was before the call shapes, the zero poles and
+# k_iov: N_BASE cases, each with call="plain". An id is a position, and the child seeds
+# a case's bytes from it, so cases are only ever appended: first the call shapes and
+# poles of the planner's kernels, derived from the base cases (_call_shapes_and_poles,
+# called at the end of the module), then the k_iov cases (_iov_cases).
+# ---------------------------------------------------------------------------
+N_BASE = 1592
+assert len(CASES) == N_BASE
+
+# The word a pole_data case solves for: an even packet offset the mode sums that is not
+# the checksum field, TCP's byte 12 or IPv4's byte 0.
+POLE_W = {"udp": 0, "tcp": 0, "verify_tcp": 0, "verify_udp": 0, "icmp": 4, "ipv4": 4, "verify_ipv4": 4}
+TX_POLE = ("udp", "tcp", "icmp", "ipv4")  # these sit at 0x0000, RAW and the VERIFY modes at 0xFFFF
+NO_SIDE = ("ipv4", "verify_ipv4", "icmp", "verify_rx", "tx_datagram")  # initial and addrs are ignored
+DGRAM = ("verify_rx", "tx_datagram")
+POLE_KINDS = ("pole_side", "pole_data")
+
+
+def calls(case):
+    """The call shapes of a case: {"plain"}, or a subset of {"offset", "null_out", "ignored"}."""
+    return set(case["call"].split("+"))
+
+
+def pole(mode):
+    return 0x0000 if mode in TX_POLE else 0xFFFF
+
+
+def ignores(mode, side):
+    """What an `ignored` case adds as junk: "both" arrays (and initial = 0xBEEF), "addrs"
+    (RAW), "init" (a pseudo mode given addrs, with initial = 0xBEEF); None: nothing to ignore."""
+    if mode in NO_SIDE:
+        return "both"
+    if mode == "raw":
+        return "addrs"
+    return "init" if side == "addrs" else None
+
+
+def _template(kernel, form, fill, layout, mode, wrap, need, most):
+    """The smallest base case of this key and mode (uniform: with need <= len <= most)."""
+    found = [c for c in CASES[:N_BASE] if kernel_of(c) == (kernel, form) and c["fill"] == fill and
+             c["layout"] == layout and c["mode"] == mode and (c["n"] == "n_wrap") == wrap and
+             (layout == "R" or need <= c["len"] <= most)]
+    return min(found, key=lambda c: case_bytes(c, _small_n(c)), default=None)
+
+
+def _small_n(t):
+    """The smallest count at which the template's kernel is still the planner's pick:
+    37 for the per-packet kernels, 4097 for the c16 kinds, MID_BATCH + 1 for the 64-, 48-
+    and 40-packet chunk kinds; the far-stride k_small cases keep their two packets."""
+    if t["layout"] == "U" and t["stride"] == _FAR:
+        return t["n"]
+    return MID_BATCH + 1 if t["n_lo"] == MID_BATCH else max(t["n_lo"], 37)
+
+
+def _derive(kernel, form, fill, layout, modes, *, call, kind="rand", sides=("init", "addrs", "scalar"), wrap=False):
+    """Appends one case of the key (kernel, form, fill, layout): the first of `modes` x
+    `sides` the key's base cases hold, with that base case's geometry (ragged: short
+    packets), at the smallest count, under one of the base case's knob sets."""
+    for mode in modes:
+        side = next((s for s in sides if s in SIDES.get(mode, ("scalar",))), None)
+        if side is None:
+            continue
+        need = max(MIN_LEN.get(mode, 0), POLE_W[mode] + 2 if kind == "pole_data" else 0)
+        t = _template(kernel, form, fill, layout, mode, wrap, need, 65535 if kind == "pole_side" else 1 << 32)
+        if t is None:
+            continue
+        sets = sorted(s for s in t["plans"] if s or not wrap)
+        s = sets[len(CASES) % len(sets)]
+        c = dict(t, call=call, kind=kind, side=side, n="n_wrap" if wrap else _small_n(t), plans={s: t["plans"][s]})
+        if layout == "R":
+            c["gen"] = (("dgram", 0, 180) if mode in DGRAM else ("range", 0, 200) if mode == "raw" else
+                        ("range", max(_RLO[mode], need), 120 if wrap else 200))
+        _append(c)
+        return True
+    return False
+
+
+def _rot(modes):
+    modes = sorted(modes)
+    k = len(CASES) % max(len(modes), 1)
+    return modes[k:] + modes[:k]
+
+
+def _call_shapes_and_poles():
+    keys = {}  # kernel -> {(form, fill, layout): modes}
+    for c in CASES[:N_BASE]:
+        keys.setdefault(kernel_of(c)[0], {}).setdefault((kernel_of(c)[1], c["fill"], c["layout"]), set()).add(c["mode"])
+    for kernel in sorted(keys):
+        ks = keys[kernel]
+        # read-only keys first: a kernel that only writes in place (the TXW kinds) is held by those
+        order = sorted(ks, key=lambda k: (k[1], k[0], k[2]))
+        per_layout = {lay: next(k for k in order if k[2] == lay) for lay in sorted({k[2] for k in order})}
+        some = order[0]
+        # 1. offset: out and every side array the kernel's modes take, in each layout it takes
+        #    (ragged: offsets too), at the least alignment include/yucsum.h allows
+        for lay, k in per_layout.items():
+            took = [_derive(kernel, *k, _rot(ks[k]), call="offset", sides=(side,)) for side in ("init", "addrs")]
+            if not any(took):
+                assert _derive(kernel, *k, _rot(ks[k]), call="offset"), (kernel, k)
+        # 2. ignored: junk in every argument the mode does not use
+        took = [_derive(kernel, *some, _rot(ks[some] & set(NO_SIDE)), call="ignored"),
+                _derive(kernel, *some, ["raw"], call="ignored", sides=("init", "scalar")),
+                _derive(kernel, *some, _rot(ks[some] - {"raw"}), call="ignored", sides=("addrs",))]
+        assert any(took), kernel
+        # 3. null_out: every in-place key without a result array, side arrays at the offset
+        #    alignments; once per (kernel, form) across a second pass of the grid
+        wrapped = set()
+        for k in order:
+            if not k[1]:
+                continue
+            assert _derive(kernel, *k, _rot(ks[k]), call="offset+null_out"), (kernel, k)
+            if k[0] not in wrapped and _derive(kernel, *k, _rot(ks[k]), call="null_out", wrap=True):
+                wrapped.add(k[0])
+        # 4. pole_side: initial_arr puts every packet on its pole (TX: 0x0000, RAW / VERIFY: 0xFFFF)
+        for modes in ({"udp", "tcp"}, {"raw", "verify_tcp", "verify_udp"}):
+            took = [k for k in order if ks[k] & modes]
+            assert not took or any(_derive(kernel, *k, _rot(ks[k] & modes), call="plain", kind="pole_side",
+                                           sides=("init",)) for k in took), (kernel, modes)
+        # 5. pole_data: one word of the packet puts it on its pole (the pseudo modes: with
+        #    addrs); the TX and IPv4 modes read-only and in place, then a VERIFY mode
+        for fill in (False, True):
+            took = [k for k in order if k[1] == fill and ks[k] & set(TX_POLE)]
+            assert not took or any(_derive(kernel, *k, _rot(ks[k] & set(TX_POLE)), call="plain", kind="pole_data",
+                                           sides=("addrs", "scalar")) for k in took), (kernel, fill)
+        for k in order:
+            if ks[k] & {"verify_ipv4", "verify_tcp", "verify_udp"} and _derive(
+                    kernel, *k, _rot(ks[k] & {"verify_ipv4", "verify_tcp", "verify_udp"}), call="plain",
+                    kind="pole_data", sides=("addrs", "scalar")):
+                break
+        # 6. all-zero and all-0xFF packets in place (ICMP lands on the poles: 0xFFFF and 0x0000)
+        for form in sorted({k[0] for k in order if k[1]}):
+            k = next(k for k in order if k[1] and k[0] == form)
+            if ks[k] <= set(DGRAM):
+                continue
+            for kind in ("zero", "ff"):
+                assert _derive(kernel, *k, ["icmp"] + _rot(ks[k]), call="plain", kind=kind), (kernel, k)
+
+
 def resolve_n(case, cus, env):
     """The case's packet count on a card with `cus` CUs under the knob set `env`. n_wrap:
     the smallest n above 4 * ppw * CUs * blocks_per_cu + ppw, so that under
@@ -389,6 +551,8 @@ def resolve_n(case, cus, env):
 
 def case_bytes(case, n):
     """An upper bound of the bytes the case moves (the packet buffer)."""
+    if case["layout"] == "I":
+        return n * (1500 + 64 if case["iov"] == "hdr+pay" else 40 * 32)
     if case["layout"] == "U":
         return case["base"] + (n - 1) * case["stride"] + case["len"]
     name, lo, hi = case["gen"]
@@ -401,3 +565,91 @@ def query_line(case, n, cus):
     u = case["layout"] == "U"
     return "%s %s %d %d %d %d %d %d" % (case["layout"], case["mode"], case["base"] if u else 0,
                                         case["stride"] if u else 0, case["len"] if u else 0, n, case["fill"], cus)
+
+
+_call_shapes_and_poles()
+
+
+# ---------------------------------------------------------------------------
+# Layout "I": k_iov<4> / k_iov<4,fill>, the scatter-gather device calls (yu::plan_iov: a
+# wave per packet at every count, the policy slot YU_NT's, else 2). A packet is a list of
+# (pool, alignment mod 16, length) views, the form of iov_layout.general_layout; the child
+# builds the yu_iovec table and first_iov by hand. Under the default set and the RUNS0 trio.
+# ---------------------------------------------------------------------------
+IOV_KERNELS = ("k_iov<4>", "k_iov<4,fill>")
+IOV_SHAPES = ("hdr+pay", "split", "bytes40", "empty")
+IOV_MODES = PLAIN6
+
+
+def iov_packets(case, n):
+    """The views of the n packets of an "I" case. hdr+pay: a 20-byte and a 1480-byte view
+    in two pools; split: a small datagram cut inside its checksum field (RAW and the
+    VERIFY modes: where UDP's lies); bytes40: forty 1-byte views; empty: two views with
+    empty ones before, between and after (and, where the mode defines them, packets of
+    empty views only)."""
+    mode, shape = case["mode"], case["iov"]
+    f = FIELD.get(mode, 6)
+    need = MIN_LEN.get(mode, 0)
+    packets = []
+    for i in range(n):
+        a, b = (5 * i) % 16, (3 * i + 1) % 16
+        if shape == "hdr+pay":
+            packets.append([(0, a, 20), (1, b, 1480)])
+        elif shape == "split":
+            packets.append([(0, a, f + 1), (1, b, max(need, f + 2) + (7 * i) % 64 - f - 1)])
+        elif shape == "bytes40":
+            packets.append([(j % 2, (a + j) % 16, 1) for j in range(40)])
+        elif need == 0 and i % 7 == 3:
+            packets.append([(0, 0, 0), (1, 0, 0)])
+        else:
+            packets.append([(0, 0, 0), (0, a, 21), (1, 0, 0), (1, 0, 0), (1, b, 33 + i % 5), (0, 0, 0)])
+    return packets
+
+
+def I(mode, shape, n, sets, *, fill=False, **kw):
+    assert shape in IOV_SHAPES and mode in (FILL3 if fill else IOV_MODES)
+    _add("I", IOV_KERNELS[fill], "plain", mode, sets, n, 1, fill=fill, iov=shape, **kw)
+
+
+def _iov_cases():
+    both = DEFAULT + RUNS0
+    k = 0
+    for shape in IOV_SHAPES:  # counts 1, 2 and 37, every mode in turn
+        for n in (1, 2, 37):
+            I(IOV_MODES[k % 6], shape, n, both)
+            k += 1
+        I(FILL3[k // 3 % 3], shape, 37, both, fill=True)
+    I("udp", "split", 1, both, fill=True)
+    I("tcp", "split", 2, both, fill=True)
+    # a second, partial pass of the grid under one block per CU (a wave per packet)
+    I("tcp", "hdr+pay", "n_wrap", RUNS0, side="addrs")
+    I("raw", "empty", "n_wrap", RUNS0, side="init")
+    I("udp", "split", "n_wrap", RUNS0, fill=True, side="addrs")
+    I("icmp", "bytes40", "n_wrap", RUNS0, fill=True, call="null_out")
+    # the call shapes: the table and first_iov at 8 (mod 16) too
+    I("raw", "hdr+pay", 37, both, side="init", call="offset")
+    I("verify_tcp", "split", 37, both, side="addrs", call="offset")
+    I("udp", "split", 37, both, fill=True, side="addrs", call="offset")
+    I("tcp", "hdr+pay", 37, both, fill=True, side="init", call="offset+null_out")
+    I("icmp", "empty", 37, both, fill=True, call="offset+null_out")
+    I("icmp", "split", 37, both, call="ignored")
+    I("raw", "empty", 37, both, side="init", call="ignored")
+    I("verify_udp", "hdr+pay", 37, both, side="addrs", call="ignored")
+    I("icmp", "bytes40", 37, both, fill=True, call="ignored")
+    # the zero poles
+    I("udp", "split", 37, both, side="init", kind="pole_side")
+    I("tcp", "hdr+pay", 37, both, fill=True, side="init", kind="pole_side")
+    I("raw", "empty", 37, both, side="init", kind="pole_side")
+    I("verify_tcp", "bytes40", 37, both, side="init", kind="pole_side")
+    I("udp", "split", 37, both, side="addrs", kind="pole_data")
+    I("icmp", "hdr+pay", 37, both, kind="pole_data")
+    I("tcp", "split", 37, both, fill=True, side="addrs", kind="pole_data")
+    I("verify_udp", "bytes40", 37, both, side="addrs", kind="pole_data")
+    I("icmp", "bytes40", 37, both, fill=True, kind="pole_data")
+    I("icmp", "split", 37, both, fill=True, kind="zero")
+    I("icmp", "split", 37, both, fill=True, kind="ff")
+    I("raw", "empty", 37, both, side="scalar", kind="zero")
+    I("udp", "hdr+pay", 37, both, fill=True, side="scalar", kind="ff")
+
+
+_iov_cases()

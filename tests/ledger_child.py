@@ -2,11 +2,29 @@
     python tests/ledger_child.py <knob set index>
 The knobs are in the environment already (tests/test_gpu_kernel_ledger.py sets them:
 the library reads them once). Per case: the library names the written kernel; the results
-equal the C oracle's on the same bytes; the 64 guard entries after the results are
-untouched; in place, the packets are a view into a buffer with 128 guard bytes on each
-side, and afterwards every byte of that buffer equals the input except the fields the
-oracle defines, which hold its values big-endian. One line per case; exits non-zero at
-the first mismatch."""
+equal the C oracle's on the same bytes; `out` lies inside an allocation with 64 guard
+entries on each side, which are untouched; the packets are a view into a buffer with 128
+guard bytes on each side (scatter-gather: every pool), and afterwards every byte of it
+equals the input except, in place, the fields the oracle defines, which hold its values
+big-endian. One line per case; exits non-zero at the first mismatch.
+
+A case's `call` says how the call is made. "plain": through yustack_amd.batch, `out` 128-byte
+aligned. Otherwise through the C ABI (yustack_amd._lib.lib()) with pointers into guarded
+allocations (Placed) that are compared afterwards: "offset" puts out and initial_arr at
+2 (mod 4), addrs at 4 (mod 8) (4 or 12 mod 16 by case index), offsets, the yu_iovec table
+and first_iov at 8 (mod 16), asserted before the call; "null_out" passes out = NULL to the
+in-place call (the packet memory is the evidence); "ignored" passes junk arrays, at those
+alignments, and initial = 0xBEEF in the arguments the mode does not use, while the oracle
+gets only the ones it uses. The scatter-gather cases (layout "I") always take the C ABI,
+with the table written here.
+
+A case's `kind` beyond the byte patterns: "pole_side" and "pole_data" solve initial_arr or
+one word of every packet with the oracle so that every packet sums to 0x0000 (the TX modes)
+or 0xFFFF (RAW, VERIFY_*); prepare() refuses a case with a packet off its pole. An all-zero
+packet written in place first gets random nonzero bytes in its field.
+
+prepare, expected_memory, check_out and check_memory need no GPU: tests/test_kernel_ledger.py
+feeds them wrong results."""
 import os
 import sys
 import time
@@ -19,6 +37,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 
 import kernel_cases as K  # noqa: E402
 import rxgen  # noqa: E402
+from iov_layout import general_layout, set_tcp_offset  # noqa: E402
 
 GUARD = 128
 OUT_GUARD = 64
@@ -108,7 +127,7 @@ def build(case, n, rng):
             slots = np.lib.stride_tricks.as_strided(buf[GUARD + base:], (n, ln), (st, 1))
             slots[:] = pool[rng.integers(0, len(pool), size=n)]
         elif ln:
-            headers(rng, buf, starts, ln, mode, case["fill"])
+            headers(rng, buf, starts, ln, mode, case["fill"] or case["kind"] == "pole_data")
         return buf, starts, starts + ln
     name, lo, hi = case["gen"]
     if dgram:
@@ -129,64 +148,232 @@ def build(case, n, rng):
     if dgram:
         buf[GUARD + base:int(offs[-1])] = np.concatenate(parts) if parts else 0
     else:
-        headers(rng, buf, offs[:-1], lens, mode, case["fill"])
+        headers(rng, buf, offs[:-1], lens, mode, case["fill"] or case["kind"] == "pole_data")
     return buf, offs[:-1], offs[1:]
+
+
+class Prepared:
+    """A case as far as the CPU takes it (prepare)."""
+
+
+def prepare(case, s, cus, oracle):
+    """The bytes, the side data and the oracle's values of a case under knob set `s`;
+    a string when the case itself is wrong (a pole case off its pole)."""
+    P = Prepared()
+    P.n = n = K.resolve_n(case, cus, K.KNOB_SETS[s])
+    mode, fill, kind, layout = case["mode"], case["fill"], case["kind"], case["layout"]
+    P.index = int(case["id"].split()[0])
+    rng = np.random.default_rng(P.index * 16 + s)
+    P.k = 2 if mode == "tx_datagram" else 1
+    P.lay = P.buf = None
+    if layout == "I":
+        P.lay = lay = general_layout(K.iov_packets(case, n), rng, fillbyte={"zero": 0, "ff": 255}.get(kind))
+        if mode in ("tcp", "verify_tcp") and kind in ("zero", "ff"):
+            set_tcp_offset(lay)
+        P.starts, P.ends = lay.offsets[:-1].astype(np.int64), lay.offsets[1:].astype(np.int64)
+        put = lay.put
+    else:
+        P.buf, P.starts, P.ends = build(case, n, rng)
+
+        def put(pos, values):
+            P.buf[pos] = values
+    starts, lens = P.starts, P.ends - P.starts
+    side = case["side"]
+    P.init = rng.integers(0, 65536, size=n, dtype=np.uint16) if side == "init" else None
+    P.addrs = rng.integers(0, 256, size=8 * n, dtype=np.uint8) if side == "addrs" else None
+    P.initial = initial = 0x1234 if side == "scalar" and mode in K.SIDES else 0
+    threads = 8 if (P.buf.size if P.buf is not None else lay.bpos.size) > (1 << 20) else 1
+
+    def ask(init):
+        if layout == "U":
+            return oracle.batch(P.buf[GUARD + case["base"]:], K.MODES.index(mode), stride=case["stride"],
+                                length=case["len"], n=n, initial_arr=init, initial=initial, addrs=P.addrs, threads=threads)
+        if layout == "R":
+            return oracle.batch(P.buf[GUARD:], K.MODES.index(mode), offsets=P.offs, initial_arr=init, initial=initial,
+                                addrs=P.addrs, threads=threads)
+        return oracle.batch(lay.blob(), K.MODES.index(mode), offsets=lay.offsets, initial_arr=init, initial=initial,
+                            addrs=P.addrs, threads=threads)
+
+    if layout == "R":
+        P.offs = np.append(starts, P.ends[-1:]).astype(np.uint64) - GUARD
+    if kind == "zero" and fill and mode in K.FIELD:
+        # a nonzero stored field: "the field is taken as 0" is what keeps the packet all-zero
+        at = starts[lens >= K.FIELD[mode] + 2] + K.FIELD[mode]
+        put(at, rng.integers(1, 256, size=at.size, dtype=np.uint8))
+        put(at + 1, rng.integers(1, 256, size=at.size, dtype=np.uint8))
+    if kind == "pole_data":
+        # the word at POLE_W: zeroed, then the oracle's value (VERIFY: its complement) stored there
+        w = K.POLE_W[mode]
+        if (lens < w + 2).any():
+            return f"test bug: a packet shorter than {w + 2} bytes in a pole_data case"
+        put(starts + w, 0)
+        put(starts + w + 1, 0)
+        r = ask(P.init)
+        r = r if mode in K.TX_POLE else ~r & 0xFFFF
+        put(starts + w, (r >> 8).astype(np.uint8))
+        put(starts + w + 1, (r & 0xFF).astype(np.uint8))
+    if kind == "pole_side":
+        # initial_arr: the oracle's value with initial_arr all 0 (RAW / VERIFY: its complement)
+        if mode == "raw" and (lens > 65535).any():
+            return "test bug: a RAW packet above 65535 bytes in a pole_side case"
+        r0 = ask(np.zeros(n, np.uint16))
+        P.init = r0 if mode in K.TX_POLE else (~r0 & 0xFFFF).astype(np.uint16)
+    P.want = want = ask(P.init)
+    if kind in K.POLE_KINDS and not (want == K.pole(mode)).all():
+        off = np.nonzero(want != K.pole(mode))[0]
+        return f"test bug: {off.size} packets off the pole {K.pole(mode):#06x}, first {off[:6].tolist()}"
+    if fill and mode == "icmp" and kind in ("zero", "ff"):  # all-zero: 0xFFFF; all-0xFF, even length: 0x0000
+        on = want == 0xFFFF if kind == "zero" else want[lens % 2 == 0] == 0
+        if not on.all():
+            return f"test bug: an all-{kind} ICMP packet off its pole"
+    # `ignored`: junk in the arguments the mode does not use; the oracle never sees it
+    P.junk_init = P.junk_addrs = None
+    P.call_initial = initial
+    what = K.ignores(mode, side) if "ignored" in K.calls(case) else None
+    if what in ("both", "init"):
+        P.junk_init = rng.integers(0, 65536, size=n, dtype=np.uint16)
+        P.call_initial = 0xBEEF
+    if what in ("both", "addrs"):
+        P.junk_addrs = rng.integers(0, 256, size=8 * n, dtype=np.uint8)
+    return P
+
+
+def expected_memory(case, P):
+    """The packet memory after the call: the buffer (uniform, ragged) or the list of
+    pools (scatter-gather), the input but for the fields the oracle defines."""
+    mode = case["mode"]
+    if P.lay is not None:
+        return P.lay.filled(K.MODES.index(mode), P.want) if case["fill"] else P.lay.pools
+    if not case["fill"]:
+        return P.buf
+    exp = P.buf.copy()
+    if mode == "tx_datagram":
+        pos, val = datagram_fields(P.buf, P.starts, P.ends, P.want)
+    else:
+        pos, val = P.starts + K.FIELD[mode], P.want
+    exp[pos] = (val >> 8).astype(np.uint8)
+    exp[pos + 1] = (val & 0xFF).astype(np.uint8)
+    return exp
+
+
+def check_out(got, lo, want):
+    """`got`: the whole result allocation, guards included; the results start at entry lo."""
+    res = got[lo:lo + want.size]
+    if not np.array_equal(res, want):
+        bad = np.nonzero(res != want)[0]
+        return f"{bad.size} results differ, first at {bad[:6].tolist()}: got {res[bad[:3]].tolist()} want {want[bad[:3]].tolist()}"
+    if not (got[:lo] == OUT_FILL).all():
+        return f"guard entries before the results changed: {np.nonzero(got[:lo] != OUT_FILL)[0][:6].tolist()}"
+    if not (got[lo + want.size:] == OUT_FILL).all():
+        return f"guard entries after the results changed: {np.nonzero(got[lo + want.size:] != OUT_FILL)[0][:6].tolist()}"
+    return None
+
+
+def check_memory(after, exp, what="the expected buffer"):
+    if not np.array_equal(after, exp):
+        bad = np.nonzero(after != exp)[0]
+        return f"{bad.size} bytes differ from {what}, first at {(bad[:6] - GUARD).tolist()} (view offsets)"
+    return None
+
+
+class Placed:
+    """A host array in device memory at an address congruent to `mod` (mod `align`),
+    with guard bytes on both sides."""
+
+    def __init__(self, torch, dev, payload, mod, align):
+        raw = np.ascontiguousarray(payload).view(np.uint8).reshape(-1)
+        self.t = torch.empty(GUARD + align + raw.size + GUARD, dtype=torch.uint8, device=dev)
+        off = GUARD + (mod - (self.t.data_ptr() + GUARD)) % align
+        self.host = np.full(self.t.numel(), 0xA5, np.uint8)
+        self.host[off:off + raw.size] = raw
+        self.t.copy_(torch.from_numpy(self.host))
+        self.ptr = self.t.data_ptr() + off
+        assert self.ptr % align == mod and off + raw.size + GUARD <= self.t.numel()
+
+    def changed(self):
+        return not np.array_equal(self.t.cpu().numpy(), self.host)
 
 
 def run_case(case, s, cus, dev, oracle, torch, batch):
     env = K.KNOB_SETS[s]
     n = K.resolve_n(case, cus, env)
-    mode, fill = case["mode"], case["fill"]
-    rng = np.random.default_rng(int(case["id"].split()[0]) * 16 + s)
+    mode, fill, layout = case["mode"], case["fill"], case["layout"]
     kernel = case["plans"][s].split()[0]
-    uniform = case["layout"] == "U"
-    name = (batch.variant(case["stride"], case["len"], mode, case["base"], n=n) if uniform
-            else batch.ragged_variant(mode, n, fill=fill))
+    name = (batch.variant(case["stride"], case["len"], mode, case["base"], n=n) if layout == "U" else
+            batch.ragged_variant(mode, n, fill=fill) if layout == "R" else batch.iov_variant(mode, n, fill=fill))
     if name != kernel:
         return f"the library names {name}"
-    buf, starts, ends = build(case, n, rng)
-    side = case["side"]
-    init = rng.integers(0, 65536, size=n, dtype=np.uint16) if side == "init" else None
-    addrs = rng.integers(0, 256, size=8 * n, dtype=np.uint8) if side == "addrs" else None
-    initial = 0x1234 if side == "scalar" and mode in K.SIDES else 0
-    k = 2 if mode == "tx_datagram" else 1
-    threads = 8 if buf.size > (1 << 20) else 1
-    view = buf[GUARD:]
-    if uniform:
-        want = oracle.batch(view[case["base"]:], K.MODES.index(mode), stride=case["stride"], length=case["len"], n=n,
-                            initial_arr=init, initial=initial, addrs=addrs, threads=threads)
+    P = prepare(case, s, cus, oracle)
+    if isinstance(P, str):
+        return P
+    shapes = K.calls(case)
+    offset = "offset" in shapes
+    want = P.want
+    # out: inside an allocation with OUT_GUARD entries on both sides; 128-byte aligned, or at 2 (mod 4)
+    lo = OUT_GUARD + (1 if offset else 0)
+    big = torch.from_numpy(np.full(lo + n * P.k + OUT_GUARD, OUT_FILL, np.uint16)).to(dev)
+    out_ptr = big.data_ptr() + 2 * lo
+    assert out_ptr % 4 == 2 if offset else out_ptr % 128 == 0
+    if P.lay is None:
+        whole = torch.from_numpy(P.buf).to(dev)
+        memory = [whole]
     else:
-        offs = np.append(starts, ends[-1:]).astype(np.uint64) - GUARD
-        want = oracle.batch(view, K.MODES.index(mode), offsets=offs, initial_arr=init, initial=initial, addrs=addrs,
-                            threads=threads)
-    whole = torch.from_numpy(buf).to(dev)
-    out = torch.from_numpy(np.full(n * k + OUT_GUARD, OUT_FILL, np.uint16)).to(dev)
-    side_t = dict(initial=initial, initial_arr=None if init is None else torch.from_numpy(init).to(dev),
-                  addrs=None if addrs is None else torch.from_numpy(addrs).to(dev), out=out, fill=fill)
-    if uniform:
-        batch.checksum_uniform(whole[GUARD + case["base"]:], case["stride"], case["len"], n, mode, **side_t)
-    else:
-        batch.checksum_ragged(whole[GUARD:], torch.from_numpy(offs.view(np.int64)).to(dev), mode, **side_t)
-    got = out.cpu().numpy()
-    if not np.array_equal(got[:n * k], want):
-        bad = np.nonzero(got[:n * k] != want)[0]
-        return f"{bad.size} results differ, first at {bad[:6].tolist()}: got {got[bad[:3]].tolist()} want {want[bad[:3]].tolist()}"
-    if not (got[n * k:] == OUT_FILL).all():
-        return f"guard entries after the results changed: {np.nonzero(got[n * k:] != OUT_FILL)[0][:6].tolist()}"
-    after = whole.cpu().numpy()
-    exp = buf
-    if fill:
-        exp = buf.copy()
-        if mode == "tx_datagram":
-            pos, val = datagram_fields(buf, starts, ends, want)
+        memory = [torch.from_numpy(p).to(dev) for p in P.lay.pools]
+    if shapes == {"plain"} and P.lay is None:  # through the Python front end
+        side_t = dict(initial=P.initial, initial_arr=None if P.init is None else torch.from_numpy(P.init).to(dev),
+                      addrs=None if P.addrs is None else torch.from_numpy(P.addrs).to(dev), out=big[lo:lo + n * P.k],
+                      fill=fill)
+        if layout == "U":
+            batch.checksum_uniform(whole[GUARD + case["base"]:], case["stride"], case["len"], n, mode, **side_t)
         else:
-            pos, val = starts + K.FIELD[mode], want
-        exp[pos] = (val >> 8).astype(np.uint8)
-        exp[pos + 1] = (val & 0xFF).astype(np.uint8)
-    if not np.array_equal(after, exp):
-        bad = np.nonzero(after != exp)[0]
-        return f"{bad.size} bytes differ from the expected buffer, first at {(bad[:6] - GUARD).tolist()} (view offsets)"
-    return None
+            batch.checksum_ragged(whole[GUARD:], torch.from_numpy(P.offs.view(np.int64)).to(dev), mode, **side_t)
+        placed = []
+    else:  # the C ABI itself: pointers at the least alignment it allows, NULL out, junk in unused arguments
+        from yustack_amd import _lib
+        init = P.init if P.init is not None else P.junk_init
+        addrs = P.addrs if P.addrs is not None else P.junk_addrs
+        # the arrays the mode reads: at the least alignment when `offset`; junk ones always
+        low_i, low_a = offset or P.init is None, offset or P.addrs is None
+        pi = None if init is None else Placed(torch, dev, init, 2 if low_i else 0, 4 if low_i else 256)
+        pa = None if addrs is None else Placed(torch, dev, addrs, (4, 12)[P.index % 2] if low_a else 0, 16 if low_a else 256)
+        placed = [x for x in (pi, pa) if x is not None]
+        assert pi is None or not low_i or pi.ptr % 4 == 2
+        assert pa is None or not low_a or (pa.ptr % 8 == 4 and pa.ptr % 16 == (4, 12)[P.index % 2])
+        tail = (None if pi is None else pi.ptr, P.call_initial, None if pa is None else pa.ptr,
+                None if "null_out" in shapes else out_ptr, torch.cuda.current_stream(dev).cuda_stream)
+        L = _lib.lib()
+        if layout == "U":
+            data = whole.data_ptr() + GUARD + case["base"]
+            assert not fill or (data % 4 == 0 and case["stride"] % 4 == 0)
+            rc = (L.yu_csum_fill_uniform if fill else L.yu_csum_batch_uniform)(
+                data, case["stride"], case["len"], n, K.MODES.index(mode), *tail)
+        else:
+            if layout == "R":
+                tables = [P.offs]
+                first_arg = whole.data_ptr() + GUARD
+            else:  # the yu_iovec table {base, len} and first_iov; empty views: NULL and wild bases
+                lay = P.lay
+                base = np.array([t.data_ptr() for t in memory], np.uint64)[lay.vp] + np.uint64(GUARD) + lay.vo.astype(np.uint64)
+                base[lay.vl == 0] = np.where(np.arange(lay.vl.size) % 2, 0xDEAD0001, 0).astype(np.uint64)[lay.vl == 0]
+                tables = [np.stack((base, lay.vl.astype(np.uint64)), 1), lay.first.astype(np.uint64)]
+                first_arg = None
+            pt = [Placed(torch, dev, t, 8 if offset else 0, 16 if offset else 256) for t in tables]
+            placed += pt
+            assert not offset or all(x.ptr % 16 == 8 for x in pt)
+            f = getattr(L, "yu_csum_%s_%s" % ("fill" if fill else "batch", "ragged" if layout == "R" else "iov"))
+            rc = f(first_arg if layout == "R" else pt[0].ptr, pt[-1].ptr, n, K.MODES.index(mode), *tail)
+        if rc != 0:
+            return f"status {rc}"
+    err = None if "null_out" in shapes else check_out(big.cpu().numpy(), lo, want)
+    if err is None and "null_out" in shapes and not (big.cpu().numpy() == OUT_FILL).all():
+        err = "the result allocation changed in a call without out"
+    exp = expected_memory(case, P)
+    for k, t in enumerate(memory):
+        err = err or check_memory(t.cpu().numpy(), exp[k] if P.lay is not None else exp,
+                                  f"the expected pool {k}" if P.lay is not None else "the expected buffer")
+    if err is None and any(x.changed() for x in placed):
+        err = "a side array, a table or its guard bytes changed"
+    return err
 
 
 def main():

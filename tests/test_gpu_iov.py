@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+from iov_layout import GUARD, Layout, general_layout, two_view_layout  # noqa: F401 - shared with the kernel ledger
 from oracle import oracle as O
 from test_oracle import refexec_mode_batch
 from yustack_amd import batch
@@ -26,69 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODES = (O.MODE_RAW, O.MODE_UDP, O.MODE_TCP, O.MODE_ICMP, O.MODE_VERIFY_TCP, O.MODE_VERIFY_UDP)
 TX = (O.MODE_UDP, O.MODE_TCP, O.MODE_ICMP)
 MIN_LEN = {O.MODE_UDP: 8, O.MODE_TCP: 20, O.MODE_ICMP: 4}
-FIELD = {O.MODE_UDP: 6, O.MODE_TCP: 16, O.MODE_ICMP: 2}
 PSEUDO = (O.MODE_UDP, O.MODE_TCP, O.MODE_VERIFY_TCP, O.MODE_VERIFY_UDP)
-GUARD = 128
-
-
-class Layout:
-    """Packets as lists of views over host pools. ``vp``/``vo``/``vl``: pool, offset
-    and length of each view; ``first``: n+1 view indices. Offsets count from the
-    start of a pool's payload: every pool carries GUARD bytes in front and behind."""
-
-    def __init__(self, pools, vp, vo, vl, first):
-        self.pools = [np.ascontiguousarray(p, dtype=np.uint8) for p in pools]
-        self.vp, self.vo, self.vl, self.first = (np.asarray(x, dtype=np.int64) for x in (vp, vo, vl, first))
-        self.n = len(self.first) - 1
-        self._sel = {}
-        # where every packet byte lies: (pool, position), in packet order
-        vid = np.repeat(np.arange(len(self.vl), dtype=np.int32), self.vl)
-        vstart = np.concatenate(([0], np.cumsum(self.vl)))
-        self.bpool = self.vp.astype(np.int8)[vid]
-        self.bpos = np.arange(vstart[-1]) + (self.vo + GUARD - vstart[:-1])[vid]
-        del vid
-        self.offsets = vstart[self.first].astype(np.uint64)
-        self.lens = np.diff(self.offsets.astype(np.int64))
-
-    def blob(self):
-        out = np.zeros(len(self.bpos) + 1, np.uint8)
-        for k, p in enumerate(self.pools):
-            sel = np.flatnonzero(self.bpool == k)
-            out[sel] = p[self.bpos[sel]]
-        return out
-
-    def at_least(self, min_len):
-        """The packets of at least min_len bytes (all of them: the layout itself)."""
-        if min_len not in self._sel:
-            keep = np.flatnonzero(self.lens >= min_len)
-            self._sel[min_len] = self if len(keep) == self.n else self.select(keep)
-        return self._sel[min_len]
-
-    def select(self, keep):
-        """The same pools and views with only the packets ``keep`` (indices)."""
-        keep = np.asarray(keep, dtype=np.int64)
-        cnt = (self.first[1:] - self.first[:-1])[keep]
-        idx = np.repeat(self.first[:-1][keep] - np.concatenate(([0], np.cumsum(cnt)[:-1])), cnt) + np.arange(cnt.sum())
-        first = np.concatenate(([0], np.cumsum(cnt)))
-        return Layout(self.pools, self.vp[idx], self.vo[idx], self.vl[idx], first)
-
-    def device(self, dev):
-        pools = [torch.from_numpy(p).to(dev) for p in self.pools]
-        views = [t[GUARD:t.numel() - GUARD] for t in pools]
-        ix = [torch.from_numpy(x).to(dev) for x in (self.vp, self.vo, self.vl, self.first)]
-        return pools, views, ix
-
-    def filled(self, mode, values):
-        """The pools after an in-place call that computed ``values``."""
-        want = [p.copy() for p in self.pools]
-        f = FIELD[mode]
-        pk = np.flatnonzero(self.lens >= f + 2)
-        for k, byte in ((0, values[pk] >> 8), (1, values[pk] & 0xFF)):
-            g = self.offsets[pk].astype(np.int64) + f + k
-            for q in range(len(want)):
-                sel = self.bpool[g] == q
-                want[q][self.bpos[g][sel]] = byte[sel].astype(np.uint8)
-        return want
 
 
 def side_args(mode, kind, n, rng, dev):
@@ -126,59 +65,6 @@ def check(lay, mode, kind, dev, rng, oracle_c, fill=False, with_out=True, min_le
     for k, (a, e) in enumerate(zip(after, expect)):
         diff = np.flatnonzero(a != e)
         assert diff.size == 0, (mode, kind, fill, k, diff[:8])
-    return lay
-
-
-def two_view_layout(lens, cuts, a1, a2, rng):
-    """Packet i: lens[i] bytes split after cuts[i]; the first view at an address
-    congruent to a1[i] mod 16 in pool 0, the second at a2[i] mod 4 in pool 1."""
-    lens, cuts, a1, a2 = (np.asarray(x, dtype=np.int64) for x in (lens, cuts, a1, a2))
-    l1, l2 = cuts, lens - cuts
-    pitch1 = (l1 + a1 + 31) // 16 * 16
-    pitch2 = (l2 + a2 + 19) // 16 * 16
-    o1 = np.concatenate(([0], np.cumsum(pitch1)[:-1])) + a1
-    o2 = np.concatenate(([0], np.cumsum(pitch2)[:-1])) + a2
-    pools = [rng.integers(0, 256, int(pitch1.sum()) + 2 * GUARD, dtype=np.uint8),
-             rng.integers(0, 256, int(pitch2.sum()) + 2 * GUARD, dtype=np.uint8)]
-    n = len(lens)
-    vp = np.tile([0, 1], n)
-    vo = np.stack((o1, o2), 1).reshape(-1)
-    vl = np.stack((l1, l2), 1).reshape(-1)
-    lay = Layout(pools, vp, vo, vl, 2 * np.arange(n + 1))
-    set_tcp_offset(lay)
-    return lay
-
-
-def set_tcp_offset(lay):
-    pk = np.flatnonzero(lay.lens >= 13)
-    g = lay.offsets[pk].astype(np.int64) + 12
-    for q, p in enumerate(lay.pools):
-        sel = lay.bpool[g] == q
-        p[lay.bpos[g][sel]] = 0x50
-
-
-def general_layout(packets, rng, npools=2, fillbyte=None, null_empty=False):
-    """packets: a list of lists of (pool, alignment mod 16, length). Views are laid
-    out in the order given; an empty view gets a wild offset (never read)."""
-    cursor = [0] * npools
-    vp, vo, vl, first = [], [], [], [0]
-    for pk in packets:
-        for pool, al, ln in pk:
-            pos = (cursor[pool] + 15) // 16 * 16 + al
-            cursor[pool] = pos + ln + 5
-            vp.append(pool)
-            vo.append(pos if ln else 0)
-            vl.append(ln)
-        first.append(len(vp))
-    pools = []
-    for c in cursor:
-        p = rng.integers(0, 256, c + 16 + 2 * GUARD, dtype=np.uint8)
-        if fillbyte is not None:
-            p[GUARD:len(p) - GUARD] = fillbyte
-        pools.append(p)
-    lay = Layout(pools, vp, vo, vl, first)
-    if fillbyte is None:
-        set_tcp_offset(lay)
     return lay
 
 

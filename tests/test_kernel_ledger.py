@@ -1,12 +1,18 @@
 """The kernel ledger (tests/kernel_cases.py) against the planner, on the CPU: every
 case's written plan is the planner's at 64, 256 and 304 CUs, the built library names the
 same kernel, and the cases cover every key (kernel, form, policy, in place, layout) the
-planner can return (tests/cpp/plan_query.cpp --reachable). tests/test_gpu_kernel_ledger.py
-runs the same cases on the GPU."""
+planner can return (tests/cpp/plan_query.cpp --reachable; layout "I", the scatter-gather
+calls: tests/cpp/iov_plan.cpp under each knob set). Every kernel is also held in every
+call shape (offset, null_out, ignored) and on the zero poles (pole_side, pole_data, all-zero
+and all-0xFF packets in place) its modes allow, and the child's comparisons are shown to
+fail on a wrong result and on a changed guard entry. tests/test_gpu_kernel_ledger.py runs
+the same cases on the GPU."""
+import hashlib
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 import kernel_cases as K
@@ -16,7 +22,11 @@ SOURCES = [os.path.join(ROOT, "tests", "cpp", "plan_query.cpp"), os.path.join(CS
 HEADERS = [os.path.join(ROOT, "tests", "cpp", "plan_rows.h"), os.path.join(CSRC, "yucsum_plan.h"),
            os.path.join(CSRC, "yucsum_internal.h")]
 BIN = os.path.join(ROOT, "tests", "cpp", "build", "plan_query")
-KERNELS = 39
+IOV_BIN = os.path.join(ROOT, "tests", "cpp", "build", "iov_plan")
+IOV_SOURCES = [os.path.join(ROOT, "tests", "cpp", "iov_plan.cpp"), os.path.join(CSRC, "yucsum_plan.cpp")]
+KERNELS = 39  # the planner's; beside them the len(K.IOV_KERNELS) = 2 of the scatter-gather calls
+ALL_KERNELS = KERNELS + len(K.IOV_KERNELS)
+BASE_IDS = "6501eef667e93d86c2948da7fa59f9b79ce87323018151057e04abaa6b27f201"
 
 
 @pytest.fixture(scope="module")
@@ -30,14 +40,49 @@ def query():
 
 
 @pytest.fixture(scope="module")
-def reachable(query):
+def iov_plan():
+    """tests/cpp/iov_plan.cpp, built as tests/test_iov_abi.py builds it; run(s, rows) asks
+    yu::plan_iov about (n, mode, fill, cus) rows under knob set s and returns (name, policy)."""
+    os.makedirs(os.path.dirname(IOV_BIN), exist_ok=True)
+    if not os.path.exists(IOV_BIN) or os.path.getmtime(IOV_BIN) < max(os.path.getmtime(p) for p in IOV_SOURCES + HEADERS):
+        r = subprocess.run(["g++", "-O2", "-std=c++17", f"-I{ROOT}/include", *HIP_HEADERS, *IOV_SOURCES, "-o", IOV_BIN],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+
+    def run(s, rows):
+        env = {k: v for k, v in os.environ.items() if not k.startswith("YU_")}
+        if s:
+            env.update(K.KNOB_SETS[s], YU_TUNING="1")
+        out = []
+        for i in range(0, len(rows), 500):
+            r = subprocess.run([IOV_BIN, *[str(x) for row in rows[i:i + 500] for x in row]], capture_output=True,
+                               text=True, timeout=60, env=env)
+            assert r.returncode == 0, r.stderr[-2000:]
+            out += [(line.split(maxsplit=3)[3], line.split()[1]) for line in r.stdout.splitlines()]
+        assert len(out) == len(rows)
+        return out
+    return run
+
+
+@pytest.fixture(scope="module")
+def reachable(query, iov_plan):
     r = subprocess.run([query, "--reachable"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [tuple(line.split()) for line in r.stdout.splitlines()]
     keys = {ln[1:] for ln in lines if ln[0] == "K"}
     defaults = {ln[1:] for ln in lines if ln[0] == "D"}
     assert len(keys) > 200 and len(defaults) > 100 and len({k[0] for k in keys}) == KERNELS
-    return keys, defaults
+    # layout "I": what yu::plan_iov returns under each knob set
+    rows = [(n, K.MODES.index(m), f, cus) for m in K.IOV_MODES for f in ((0, 1) if m in K.FILL3 else (0,))
+            for n in (1, 37, 4097, 1 << 20) for cus in (64, 256)]
+    iov = set()
+    for s in range(len(K.KNOB_SETS)):
+        for (name, policy), (_, m, f, _) in zip(iov_plan(s, rows), rows):
+            iov.add((name, "plain", policy, str(f), "I"))
+            if s == 0:
+                defaults.add((name, K.MODES[m], str(f), "I"))
+    assert {k[0] for k in iov} == set(K.IOV_KERNELS) and len(iov) == 6  # two kernels x three policy slots
+    return keys | iov, defaults
 
 
 def case_keys(cases=None):
@@ -65,11 +110,40 @@ def test_knob_sets():
     assert len({tuple(sorted(s.items())) for s in sets}) == len(sets)
 
 
+def test_the_base_cases_keep_their_ids():
+    """A case's id is its position and the child seeds its bytes from it: cases are only
+    appended (the digest: the ids of the N_BASE cases the ledger had before the call
+    shapes, the poles and k_iov)."""
+    assert K.N_BASE == 1592 and all(c["call"] == "plain" for c in K.CASES[:K.N_BASE])
+    assert [int(c["id"].split()[0]) for c in K.CASES] == list(range(len(K.CASES)))
+    assert hashlib.sha256("\n".join(c["id"] for c in K.CASES[:K.N_BASE]).encode()).hexdigest() == BASE_IDS
+
+
 def test_cases_are_well_formed():
     assert len({c["id"] for c in K.CASES}) == len(K.CASES)
     for c in K.CASES:
         assert c["plans"] and all(0 <= s < len(K.KNOB_SETS) for s in c["plans"]), c["id"]
         assert c["mode"] in K.MODES and c["side"] in K.SIDES.get(c["mode"], ("scalar",)), c["id"]
+        assert c["kind"] in ("rand", "zero", "ff", "pole_side", "pole_data"), c["id"]
+        shapes = K.calls(c)
+        assert shapes == {"plain"} or shapes <= {"offset", "null_out", "ignored"}, c["id"]
+        assert "null_out" not in shapes or c["fill"], c["id"]  # the read-only calls refuse a NULL out
+        assert "ignored" not in shapes or K.ignores(c["mode"], c["side"]), c["id"]
+        assert c["id"].endswith(c["kind"] if c["call"] == "plain" else c["kind"] + " " + c["call"]), c["id"]
+        if c["kind"] == "pole_side":
+            assert c["side"] == "init" and c["mode"] not in K.DGRAM, c["id"]
+            assert c["layout"] != "U" or c["mode"] != "raw" or c["len"] <= 65535, c["id"]
+            assert c["layout"] != "R" or c["gen"][0] == "range" and c["gen"][2] <= 65535, c["id"]
+        if c["kind"] == "pole_data":
+            assert c["mode"] in K.POLE_W and c["side"] in ("addrs", "scalar"), c["id"]
+            assert c["side"] == "addrs" or c["mode"] not in K.SIDES, c["id"]  # the pole comes out of the byte sum
+            shortest = c["len"] if c["layout"] == "U" else c["gen"][1] if c["layout"] == "R" else 40
+            assert shortest >= K.POLE_W[c["mode"]] + 2, c["id"]
+        if c["layout"] == "I":
+            assert c["mode"] in K.IOV_MODES and c["iov"] in K.IOV_SHAPES and K.kernel_of(c)[0] == K.IOV_KERNELS[c["fill"]]
+            assert not (c["kind"] in ("zero", "ff") and c["mode"] in ("tcp", "verify_tcp")), c["id"]
+            for n in (1, 37):
+                assert all(sum(v[2] for v in pk) >= K.MIN_LEN.get(c["mode"], 0) for pk in K.iov_packets(c, n)), c["id"]
         if c["n"] == "n_wrap":
             assert 0 not in c["plans"] and c["ppw"], c["id"]  # one block per CU: not the default set
         if c["layout"] == "U":
@@ -85,14 +159,19 @@ def test_cases_are_well_formed():
                 assert K.case_bytes(c, n) <= K.MAX_CASE_BYTES, (c["id"], n, K.case_bytes(c, n))
 
 
-def test_written_plans_are_the_planners(query):
+def test_written_plans_are_the_planners(query, iov_plan):
     """Kernel, form and policy of every case under every set it runs in, at three CU
-    counts (only `blocks` may differ between cards); ppw where the case states it."""
+    counts (only `blocks` may differ between cards); ppw where the case states it. Layout
+    "I": yu::plan_iov's kernel and policy (a wave per packet: ppw 1)."""
     text, want = [], []
     for s, env in enumerate(K.KNOB_SETS):
         text.append("# knobs: " + " ".join(f"{k}={v}" for k, v in env.items()))
+        mine = [(c, cus) for c in K.CASES if s in c["plans"] and c["layout"] == "I" for cus in K.CU_COUNTS]
+        rows = [(K.resolve_n(c, cus, env), K.MODES.index(c["mode"]), int(c["fill"]), cus) for c, cus in mine]
+        for (c, cus), (name, policy) in zip(mine, iov_plan(s, rows) if rows else []):
+            assert f"{name} plain {policy}" == c["plans"][s] and c["ppw"] == 1, (c["id"], s, cus, name, policy)
         for c in K.CASES:
-            if s in c["plans"]:
+            if s in c["plans"] and c["layout"] != "I":
                 for cus in K.CU_COUNTS:
                     text.append(K.query_line(c, K.resolve_n(c, cus, env), cus))
                     want.append((c, s))
@@ -120,6 +199,8 @@ for c in K.CASES:
         n = K.resolve_n(c, 256, K.KNOB_SETS[s])
         if c["layout"] == "U":
             print(batch.variant(c["stride"], c["len"], c["mode"], c["base"], n=n))
+        elif c["layout"] == "I":
+            print(batch.iov_variant(c["mode"], n, fill=c["fill"]))
         else:
             print(batch.ragged_variant(c["mode"], n, fill=c["fill"]))
 """
@@ -175,7 +256,7 @@ def test_default_cases_cover_every_default_tuple(reachable):
 def test_every_kernel_in_every_policy_and_form():
     triples = {k[:3] for k in case_keys()}
     kernels = sorted({t[0] for t in triples})
-    assert len(kernels) == KERNELS, kernels
+    assert len(kernels) == ALL_KERNELS and set(K.IOV_KERNELS) <= set(kernels), kernels
     missing = []
     for kern in kernels:
         forms = ["runs", "inter"] if kern.startswith("k_small") else ["plain", "fill"] if kern == "k_tiny<4>" \
@@ -190,7 +271,7 @@ def test_every_kernel_sees_addrs_and_initial_arr():
     for c in K.CASES:
         for plan in c["plans"].values():
             by_kernel.setdefault(plan.split()[0], []).append(c)
-    assert len(by_kernel) == KERNELS
+    assert len(by_kernel) == ALL_KERNELS
     for kern, cases in by_kernel.items():
         allowed = {side for c in cases for side in K.SIDES.get(c["mode"], ())}
         seen = {c["side"] for c in cases}
@@ -204,3 +285,140 @@ def test_every_key_has_a_second_pass():
     # the far-stride k_small cases hold two packets: no second pass at 32 MiB a packet
     missing = sorted(k for k in case_keys() - wrap if not (k[0] in ("k_small<4,1>", "k_small<8,1>") and k[3] == "1"))
     assert not missing, missing
+
+
+# ---------------------------------------------------------------------------
+# Call shapes and zero poles: what every kernel must be held in. Each rule returns the
+# kernels (and what they lack), so that a missing case is named.
+# ---------------------------------------------------------------------------
+def by_kernel(cases=None):
+    found = {}
+    for c in K.CASES if cases is None else cases:
+        found.setdefault(K.kernel_of(c)[0], []).append(c)
+    return found
+
+
+def missing_call_shapes(cases=None):
+    missing = []
+    for kern, mine in sorted(by_kernel(cases).items()):
+        # offset: out at 2 (mod 4) and every side array the kernel's modes take at its least alignment
+        off = [c for c in mine if "offset" in K.calls(c) and "null_out" not in K.calls(c)]
+        if not off:
+            missing.append(f"{kern}: no offset case with a result array")
+        for side in sorted({sd for c in mine for sd in K.SIDES.get(c["mode"], ())} - {"scalar"}):
+            if not any(c["side"] == side for c in mine if "offset" in K.calls(c)):
+                missing.append(f"{kern}: no offset case with {side}")
+        for lay in ("R", "I"):  # offsets / the view table and first_iov at 8 (mod 16)
+            if any(c["layout"] == lay for c in mine) and not any(c["layout"] == lay for c in mine if "offset" in K.calls(c)):
+                missing.append(f"{kern}: no offset case of layout {lay}")
+        if any(c["mode"] == "tx_datagram" for c in mine) and not any(c["mode"] == "tx_datagram" for c in off):
+            missing.append(f"{kern}: no TX_DATAGRAM offset case (the two 16-bit result stores)")
+        # null_out: every (kernel, form) that writes in place, and once across a second pass of the grid
+        for form in sorted({K.kernel_of(c)[1] for c in mine if c["fill"]}):
+            if not any("null_out" in K.calls(c) for c in mine if K.kernel_of(c)[1] == form):
+                missing.append(f"{kern} {form}: no null_out case")
+        # (the in-place cases of the two smallest k_small windows hold two packets 32 MiB apart: no second pass)
+        if any(c["fill"] for c in mine) and kern not in ("k_small<4,1>", "k_small<8,1>") and \
+                not any("null_out" in K.calls(c) and c["n"] == "n_wrap" for c in mine):
+            missing.append(f"{kern}: no null_out case across a second pass (n_wrap)")
+        # ignored: every kernel runs a mode with something to ignore
+        if not any("ignored" in K.calls(c) for c in mine):
+            missing.append(f"{kern}: no ignored case")
+    return missing
+
+
+def missing_poles(cases=None):
+    missing = []
+    for kern, mine in sorted(by_kernel(cases).items()):
+        if any("init" in K.SIDES.get(c["mode"], ()) for c in mine) and not any(c["kind"] == "pole_side" for c in mine):
+            missing.append(f"{kern}: no pole_side case")
+        for fill in (False, True):  # the TX and IPv4 field modes, read-only and in place where the kernel runs them
+            if any(c["mode"] in K.TX_POLE and c["fill"] == fill for c in mine) and \
+                    not any(c["kind"] == "pole_data" and c["mode"] in K.TX_POLE and c["fill"] == fill for c in mine):
+                missing.append(f"{kern}: no {'in-place' if fill else 'read-only'} pole_data case")
+        # all-zero and all-0xFF packets in place (the datagram modes are outside the pole kinds); ICMP where taken
+        for form in sorted({K.kernel_of(c)[1] for c in mine if c["fill"] and c["mode"] not in K.DGRAM}):
+            key = [c for c in mine if c["fill"] and K.kernel_of(c)[1] == form]
+            icmp = any(c["mode"] == "icmp" for c in key)
+            for kind in ("zero", "ff"):
+                if not any(c["kind"] == kind and (c["mode"] == "icmp" or not icmp) for c in key):
+                    missing.append(f"{kern} {form}: no in-place {kind} case{' in ICMP' if icmp else ''}")
+    return missing
+
+
+def test_every_kernel_in_every_call_shape():
+    assert not missing_call_shapes(), "\n".join(missing_call_shapes())
+
+
+def test_every_kernel_on_its_zero_poles():
+    assert not missing_poles(), "\n".join(missing_poles())
+
+
+def test_k_iov_cases():
+    """Layout "I": every view shape at the counts 1, 2, 37 and n_wrap, under the default
+    set and one YU_NT trio."""
+    mine = [c for c in K.CASES if c["layout"] == "I"]
+    assert 40 <= len(mine) <= 50
+    assert {c["iov"] for c in mine} == set(K.IOV_SHAPES)
+    for shape in K.IOV_SHAPES:
+        assert {1, 2, 37, "n_wrap"} <= {c["n"] for c in mine if c["iov"] == shape}, shape
+    assert all(set(c["plans"]) in ({0, *K.RUNS0}, set(K.RUNS0)) for c in mine)
+    assert {c["mode"] for c in mine} == set(K.IOV_MODES) and {c["mode"] for c in mine if c["fill"]} == set(K.FILL3)
+
+
+def test_the_rules_name_a_missing_case():
+    """The rules above fail, naming the kernel, when one appended case is taken away."""
+    def without(pred):
+        return [c for c in K.CASES if not pred(c)]
+
+    def of(kern, c):
+        return K.kernel_of(c)[0] == kern
+    got = missing_call_shapes(without(lambda c: of("k_lane<5>", c) and "null_out" in K.calls(c)))
+    assert got == ["k_lane<5> plain: no null_out case", "k_lane<5>: no null_out case across a second pass (n_wrap)"], got
+    got = missing_call_shapes(without(lambda c: of("k_seg<8,dg,c40>", c) and c["call"] == "offset"))
+    assert got and all(m.startswith("k_seg<8,dg,c40>:") for m in got), got
+    got = missing_call_shapes(without(lambda c: of("k_loop<4,BE>", c) and c["call"] == "ignored"))
+    assert got == ["k_loop<4,BE>: no ignored case"], got
+    got = missing_poles(without(lambda c: of("k_iov<4>", c) and c["kind"] == "pole_side"))
+    assert got == ["k_iov<4>: no pole_side case"], got
+    got = missing_poles(without(lambda c: of("k_seg<8,txw,c48>", c) and c["kind"] == "pole_data"))
+    assert got == ["k_seg<8,txw,c48>: no in-place pole_data case"], got
+    got = missing_poles(without(lambda c: of("k_tiny<4>", c) and c["kind"] == "ff"))
+    assert got == ["k_tiny<4> fill: no in-place ff case in ICMP"], got
+
+
+# ---------------------------------------------------------------------------
+# The child's comparisons can fail (no GPU: the "got" arrays are made here)
+# ---------------------------------------------------------------------------
+def test_the_childs_comparisons_fail_on_wrong_results():
+    import ledger_child as C
+    from oracle import oracle as O
+    case = next(c for c in K.CASES if c["kind"] == "pole_side" and c["layout"] == "U" and c["mode"] in K.TX_POLE)
+    s = next(iter(case["plans"]))
+    P = C.prepare(case, s, 256, O.C())
+    assert not isinstance(P, str), P
+    assert (P.want == 0x0000).all() and P.want.size == P.n  # every packet on the TX pole
+    lo = C.OUT_GUARD + 1
+    good = np.concatenate((np.full(lo, C.OUT_FILL, np.uint16), P.want, np.full(C.OUT_GUARD, C.OUT_FILL, np.uint16)))
+    assert C.check_out(good, lo, P.want) is None
+    flipped = good.copy()
+    flipped[lo + 5] ^= 0xFFFF  # the other representation of zero
+    assert "1 results differ, first at [5]: got [65535] want [0]" in C.check_out(flipped, lo, P.want)
+    front = good.copy()
+    front[lo - 1] = 0
+    assert "guard entries before the results changed: [%d]" % (lo - 1) in C.check_out(front, lo, P.want)
+    back = good.copy()
+    back[-1] ^= 1
+    assert "guard entries after the results changed" in C.check_out(back, lo, P.want)
+    # RAW and the VERIFY modes sit at the other pole
+    case = next(c for c in K.CASES if c["kind"] == "pole_side" and c["mode"] not in K.TX_POLE and c["n"] == 37)
+    P = C.prepare(case, next(iter(case["plans"])), 256, O.C())
+    assert (P.want == 0xFFFF).all()
+    wrong = np.concatenate((np.full(lo, C.OUT_FILL, np.uint16), P.want, np.full(C.OUT_GUARD, C.OUT_FILL, np.uint16)))
+    wrong[lo] = 0x0000
+    assert "got [0] want [65535]" in C.check_out(wrong, lo, P.want)
+    # the packet memory: one byte off, inside the packets or in a guard
+    exp = C.expected_memory(case, P)
+    after = (exp if P.lay is None else exp[0]).copy()
+    after[3] ^= 0x80
+    assert "1 bytes differ" in C.check_memory(after, exp if P.lay is None else exp[0])
