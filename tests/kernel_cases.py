@@ -11,7 +11,8 @@ A case is a dict:
   id        its position in CASES and a short description (cases are only appended: the
             child seeds a case's bytes from its position)
   layout    "U" (uniform: stride, len, base = the first packet's offset in a 128-byte
-            aligned buffer), "R" (ragged: gen = (name, lo, hi), base) or "I" (scatter-gather,
+            aligned buffer), "R" (ragged: gen = (name, lo, hi), base; ("seam", CH, T): a batch
+            of tests/seg_seams.py for a kind with CH-packet chunks and T-byte tiles) or "I" (scatter-gather,
             k_iov: iov = the view shape, iov_packets)
   mode, fill, side ("scalar" | "init" | "addrs")
   kind      "rand" | "zero" | "ff" (constant bytes), or a zero pole: "pole_side"
@@ -556,6 +557,11 @@ def case_bytes(case, n):
     if case["layout"] == "U":
         return case["base"] + (n - 1) * case["stride"] + case["len"]
     name, lo, hi = case["gen"]
+    if name == "seam":
+        # (CH, T): over the six chunk slots of seg_seams.batch at most 5 * per + 4 tiles, so per + 1/2 a
+        # chunk, and the short packets behind the last seam; RAW: four exact chunks of 128 KiB and more
+        return case["base"] + (n // lo + 1) * ((2 * seam_per(n, lo) + 1) * hi // 2 + 256) + \
+            (8 * 140000 if case["mode"] == "raw" else 0)
     extra = (n // 61 + 1) * (140000 if case["mode"] == "raw" else 9000) if name == "jumbo" else 0
     return int(case["base"] + n * ((lo + hi) / 2 + (60 if name == "dgram" else 0)) + extra)
 
@@ -653,3 +659,92 @@ def _iov_cases():
 
 
 _iov_cases()
+
+
+# ---------------------------------------------------------------------------
+# k_seg's seams (tests/seg_seams.py): every value k_seg produces is a difference of prefix
+# sums taken inside tiles of T = 1024 * U bytes that start at the chunk's b0, and the rules
+# at a tile's edge (a point at q == T, a field or a header window across two tiles, the
+# TXW kinds' whole-line write-back) are reached by the cases above almost only by chance.
+# Ragged: gen = ("seam", CH, T), batches that plant every seam class of the kind, at the
+# smallest count at which the kind is the pick, at base 0 and at 1 or 3. Uniform: the dense
+# sizes at which every chunk ends on a seam, and shapes that put a TX field across one in
+# every chunk. Under the default set where it makes the pick, else the first set of the
+# key's trio.
+# ---------------------------------------------------------------------------
+N_BEFORE_SEAMS = len(CASES)
+SEAM_MAX_BYTES = 24 << 20
+
+
+def seg_shape(kernel):
+    """(CH, T, kind) of a k_seg instantiation's name: k_seg<U[,tx|txw|rx|dg][,cCH]>."""
+    args = kernel[len("k_seg<"):-1].split(",")
+    kind = next((a for a in args[1:] if not a.startswith("c")), "plain")
+    ch = next((int(a[1:]) for a in args[1:] if a.startswith("c")), 64)
+    return ch, 1024 * int(args[0]), kind
+
+
+def seam_per(n, ch):
+    """Seam classes planted per chunk (seg_seams.batch): with some 70 (class, variant)
+    plants of 4 each to place, one a chunk where there are a thousand chunks, 3 from 200
+    chunks (16 packets hold no more), 6 in the 24 chunks of a 1537-packet case."""
+    chunks = n // ch
+    return 1 if chunks >= 1000 else 3 if chunks >= 200 else 6
+
+
+def is_seam(case):
+    return case["layout"] == "R" and case["gen"][0] == "seam"
+
+
+def _seam_cases():
+    seen = set()
+    k = 0
+    rows = [(kern, ms, f, False, p, lo, hi, tr[0]) for kern, ms, f, p, _ns, lo, hi, tr in _RSEG]
+    rows += [(kern, (m,), f, fp, p, lo, hi, tr) for kern, m, f, fp, p, _ns, lo, hi, tr, uni in _DG
+             if kern.startswith("k_seg") and uni != "only"]
+    for kern, ms, f, fp, p, lo, hi, tr in rows:
+        if (kern, f) in seen:  # (the 40-packet datagram kind is the pick with and without seg4)
+            continue
+        seen.add((kern, f))
+        ch, t, kind = seg_shape(kern)
+        assert ch == p
+        seg4 = tr[0] >= 7
+        dflt = not seg4 and not (f and kind == "tx")
+        n = 1537 if seg4 else MID_BATCH + 1 if lo == MID_BATCH else 4097
+        for m in ms:
+            # the 24-chunk cases take 3: with base 1 less than half of their chunks would start on a line
+            for base in (0, 3 if seg4 else (1, 3)[k % 2]):
+                R(kern, m, ("seam", ch, t), DEFAULT if dflt else tr[:1], n, p, base=base, fill=f,
+                  fill_plain=fp, n_lo=lo, n_hi=hi)
+            k += 1
+    # uniform, dense: every chunk ends on a seam and packets inside it start on one
+    big = MID_BATCH + 1
+    for j, ln in enumerate((192, 256, 384, 512, 640)):
+        U("k_seg<4>" if ln < 448 else "k_seg<8>", "plain", ("raw", "verify_tcp", "verify_udp")[j % 3], ln, ln,
+          DEFAULT, big, 64, n_lo=MID_BATCH)
+    for j, ln in enumerate((256, 512)):
+        for f in (False, True):
+            U("k_seg<4,tx>" if ln < 448 else "k_seg<8,tx>", "plain", FILL3[(j + f) % 3], ln, ln, DEFAULT, big, 64,
+              fill=f, n_lo=MID_BATCH)
+    for f in (False, True):
+        U("k_seg<8,dg>", "plain", "tx_datagram", 256, 256, DEFAULT, big, 64, fill=f, fill_plain=f, n_lo=MID_BATCH)
+    U("k_seg<8,rx>", "plain", "verify_rx", 512, 512, DEFAULT, big, 64, n_lo=MID_BATCH)
+    U("k_seg<4,rx>", "plain", "verify_rx", 512, 512, SEG4_WB[:1], 1537, 64)
+    # 16-packet chunks: 512-byte slots make a chunk one tile, 1024-byte ones two
+    for ln in (512, 1024):
+        U("k_seg<8,rx,c16>", "plain", "verify_rx", ln, ln, DEFAULT, 4097, 16, n_lo=4097, n_hi=MID_BATCH - 1)
+        for f in (False, True):
+            U("k_seg<8,dg,c16>", "plain", "tx_datagram", ln, ln, DEFAULT, 4097, 16, fill=f, fill_plain=f, n_lo=4097,
+              n_hi=MID_BATCH - 1)
+    # a TX field across a seam in every chunk (read-only; tests/test_kernel_ledger.py confirms the lanes
+    # with the model): UDP 141, lane 29: 29 * 141 + 6 = 4095; TCP 327, lane 25: 8175 + 16 = 8191; ICMP 431,
+    # lane 19: 8189 + 2 = 8191. In place a uniform field lies at an even position: TCP 272 puts lane 15's
+    # at q == 0 of tile 1.
+    for m, ln in (("udp", 141), ("tcp", 327), ("icmp", 431)):
+        U("k_seg<4,tx>", "plain", m, ln, ln, DEFAULT, big, 64, n_lo=MID_BATCH)
+    U("k_seg<4,tx>", "plain", "tcp", 272, 272, DEFAULT, big, 64, fill=True, n_lo=MID_BATCH)
+    # 8 KiB tiles: TCP 545, lane 15: 8175 + 16 = 8191 (no UDP or ICMP length of 449..704 bytes does it)
+    U("k_seg<8,tx>", "plain", "tcp", 545, 545, DEFAULT, big, 64, n_lo=MID_BATCH)
+
+
+_seam_cases()

@@ -23,6 +23,10 @@ one word of every packet with the oracle so that every packet sums to 0x0000 (th
 or 0xFFFF (RAW, VERIFY_*); prepare() refuses a case with a packet off its pole. An all-zero
 packet written in place first gets random nonzero bytes in its field.
 
+A ragged case with gen = ("seam", CH, T) takes its packets from tests/seg_seams.py, which
+plants every seam class of the case's k_seg kind; its model of the tiling takes `data` to
+lie on a 128-byte line, which is asserted of the pointer passed.
+
 prepare, expected_memory, check_out and check_memory need no GPU: tests/test_kernel_ledger.py
 feeds them wrong results."""
 import os
@@ -37,6 +41,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 
 import kernel_cases as K  # noqa: E402
 import rxgen  # noqa: E402
+import seg_seams  # noqa: E402
 from iov_layout import general_layout, set_tcp_offset  # noqa: E402
 
 GUARD = 128
@@ -130,7 +135,12 @@ def build(case, n, rng):
             headers(rng, buf, starts, ln, mode, case["fill"] or case["kind"] == "pole_data")
         return buf, starts, starts + ln
     name, lo, hi = case["gen"]
-    if dgram:
+    if name == "seam":  # (CH, T): every seam class of the case's kind, planted (tests/seg_seams.py)
+        kind = K.seg_shape(K.kernel_of(case)[0])[2]
+        line128 = kind == "txw" and case["fill"]
+        b = seg_seams.batch(lo, hi, mode, line128, base, seg_seams.classes_for(kind, mode, line128), n, rng)
+        lens, parts = b.lens, b.parts
+    elif dgram:
         pool = datagram_pool(rng, mode, n, lo, hi)
         pick = rng.integers(0, len(pool), size=n) if n > len(pool) else np.arange(n)
         parts = [pool[i] for i in pick]
@@ -317,6 +327,8 @@ def run_case(case, s, cus, dev, oracle, torch, batch):
     if P.lay is None:
         whole = torch.from_numpy(P.buf).to(dev)
         memory = [whole]
+        # the seam model (tests/seg_seams.py) takes `data` to lie on a 128-byte line
+        assert not K.is_seam(case) or (whole.data_ptr() + GUARD) % 128 == 0
     else:
         memory = [torch.from_numpy(p).to(dev) for p in P.lay.pools]
     if shapes == {"plain"} and P.lay is None:  # through the Python front end

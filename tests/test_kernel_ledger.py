@@ -6,7 +6,8 @@ calls: tests/cpp/iov_plan.cpp under each knob set). Every kernel is also held in
 call shape (offset, null_out, ignored) and on the zero poles (pole_side, pole_data, all-zero
 and all-0xFF packets in place) its modes allow, and the child's comparisons are shown to
 fail on a wrong result and on a changed guard entry. tests/test_gpu_kernel_ledger.py runs
-the same cases on the GPU."""
+the same cases on the GPU. The seam cases (tests/seg_seams.py) are rebuilt here with the
+child's own seed and shown to sit on every seam class of their kind."""
 import hashlib
 import os
 import subprocess
@@ -27,6 +28,7 @@ IOV_SOURCES = [os.path.join(ROOT, "tests", "cpp", "iov_plan.cpp"), os.path.join(
 KERNELS = 39  # the planner's; beside them the len(K.IOV_KERNELS) = 2 of the scatter-gather calls
 ALL_KERNELS = KERNELS + len(K.IOV_KERNELS)
 BASE_IDS = "6501eef667e93d86c2948da7fa59f9b79ce87323018151057e04abaa6b27f201"
+IDS_BEFORE_SEAMS = "dcca9c025b53cd4f79f8ace791a9e4de074a8492d0e1cc0f3ad49dc862994801"  # the first 2055
 
 
 @pytest.fixture(scope="module")
@@ -117,6 +119,9 @@ def test_the_base_cases_keep_their_ids():
     assert K.N_BASE == 1592 and all(c["call"] == "plain" for c in K.CASES[:K.N_BASE])
     assert [int(c["id"].split()[0]) for c in K.CASES] == list(range(len(K.CASES)))
     assert hashlib.sha256("\n".join(c["id"] for c in K.CASES[:K.N_BASE]).encode()).hexdigest() == BASE_IDS
+    # ... and of the 2055 it had before the seam cases (call shapes, poles and k_iov included)
+    assert K.N_BEFORE_SEAMS == 2055
+    assert hashlib.sha256("\n".join(c["id"] for c in K.CASES[:2055]).encode()).hexdigest() == IDS_BEFORE_SEAMS
 
 
 def test_cases_are_well_formed():
@@ -422,3 +427,173 @@ def test_the_childs_comparisons_fail_on_wrong_results():
     after = (exp if P.lay is None else exp[0]).copy()
     after[3] ^= 0x80
     assert "1 bytes differ" in C.check_memory(after, exp if P.lay is None else exp[0])
+
+
+# ---------------------------------------------------------------------------
+# k_seg's seams (tests/seg_seams.py): the seam cases hold what they are there for. The
+# generator's parameters, for which the conditions below hold: K.seam_per (classes planted
+# per chunk: 1 from 1000 chunks, 3 from 200, 6 below), the six chunk slots of
+# seg_seams.batch, and base 3 (not 1) for the 24-chunk cases of the YU_RAGGED=seg4 kinds.
+# ---------------------------------------------------------------------------
+def seam_setup(case):
+    ch, t, kind = K.seg_shape(K.kernel_of(case)[0])
+    return ch, t, kind, kind == "txw" and case["fill"] and case["layout"] == "R"
+
+
+@pytest.fixture(scope="module")
+def seams():
+    """Every ragged seam case rebuilt as the child builds it (prepare, its seed): the
+    class counts, the chunk starts' residues, the planted datagrams, the buffer's size."""
+    import ledger_child as C
+    import seg_seams as S
+    from oracle import oracle as O
+    oracle = O.C()
+    found = {}
+    for c in K.CASES:
+        if not K.is_seam(c):
+            continue
+        ch, t, kind, line128 = seam_setup(c)
+        s = next(iter(c["plans"]))
+        P = C.prepare(c, s, 256, oracle)
+        assert not isinstance(P, str), (c["id"], P)
+        b = S.batch(ch, t, c["mode"], line128, c["base"], S.classes_for(kind, c["mode"], line128), P.n,
+                    np.random.default_rng(P.index * 16 + s))
+        assert np.array_equal(b.lens, P.ends - P.starts), c["id"]  # the same batch
+        found[c["id"]] = dict(case=c, P=P, planted=b.planted, residues=b.residues, size=P.buf.size,
+                              classes=S.classes_for(kind, c["mode"], line128),
+                              counts=S.features(P.starts, P.ends, ch, t, line128, c["mode"], P.buf, data=C.GUARD))
+    return found
+
+
+def test_seam_cases_are_what_the_issue_lists():
+    """One case or more per k_seg key of the ragged tables (kernel x in place, every mode of
+    the per-packet kinds) at base 0 and at 1 or 3, one knob set each, none on a pole; at most
+    24 MiB each; no case before them changed."""
+    mine = [c for c in K.CASES[K.N_BEFORE_SEAMS:]]
+    assert all(K.kernel_of(c)[0].startswith("k_seg") and len(c["plans"]) == 1 and c["kind"] == "rand" and
+               c["call"] == "plain" for c in mine)
+    ragged = [c for c in mine if K.is_seam(c)]
+    assert not any(K.is_seam(c) for c in K.CASES[:K.N_BEFORE_SEAMS]) and all(c["layout"] == "U" for c in mine if c not in ragged)
+    want = {(K.kernel_of(c)[0], c["fill"], c["mode"]) for c in K.CASES[:K.N_BASE]
+            if c["layout"] == "R" and K.kernel_of(c)[0].startswith("k_seg")}
+    got = {}
+    for c in ragged:
+        got.setdefault((K.kernel_of(c)[0], c["fill"], c["mode"]), []).append(c["base"])
+        assert c["gen"][1:] == K.seg_shape(K.kernel_of(c)[0])[:2], c["id"]
+        s = next(iter(c["plans"]))
+        seg4 = K.KNOB_SETS[s].get("YU_RAGGED") == "seg4"
+        assert c["n"] == (1537 if seg4 else K.MID_BATCH + 1 if c["n_lo"] == K.MID_BATCH else 4097), c["id"]
+        assert K.case_bytes(c, c["n"]) <= K.SEAM_MAX_BYTES, c["id"]
+    assert set(got) == want
+    assert all(sorted(b)[0] == 0 and sorted(b)[1] in (1, 3) and len(b) == 2 for b in got.values()), got
+    for c in mine:
+        if c["layout"] == "U":
+            assert K.case_bytes(c, c["n"]) <= 44 << 20 and c["stride"] == c["len"] and c["base"] == 0, c["id"]
+
+
+def test_seam_cases_hold_every_class_of_their_kind(seams):
+    """Every class seg_seams lists for the kind, 4 times or more, per start parity where
+    the class leaves the parity free (seg_seams.wanted says which, and why a chunk's end
+    counts 4 in all); exact: 1 to 8 chunks."""
+    import seg_seams as S
+    wrong = []
+    for cid, f in seams.items():
+        wrong += [f"{cid}: {m}" for m in S.missing(f["counts"], f["classes"])]
+        if "exact" in f["classes"] and f["counts"][("exact", 0)] + f["counts"][("exact", 1)] > 8:
+            wrong.append(f"{cid}: more than 8 exact chunks")
+        assert f["size"] <= K.case_bytes(f["case"], f["P"].n) + 2 * 128 <= K.SEAM_MAX_BYTES + 256, cid
+    assert not wrong, "\n".join(wrong[:40])
+    kinds = {K.seg_shape(K.kernel_of(f["case"])[0])[2] for f in seams.values()}
+    assert kinds == {"plain", "tx", "txw", "rx", "dg"}
+
+
+def test_seam_cases_start_half_of_their_chunks_on_a_line(seams):
+    import seg_seams as S
+    for cid, f in seams.items():
+        r = f["residues"]
+        assert np.count_nonzero(r == 0) * 2 >= r.size, (cid, np.count_nonzero(r == 0), r.size)
+        assert set(S.RESIDUES) <= set(r.tolist()), (cid, sorted(set(r.tolist())))
+
+
+def test_planted_datagrams_are_in_contract(seams):
+    """From the bytes: 20 <= hl <= tl <= len for every datagram a class was planted with
+    (short_hdr is the class of IHL 0..4: outside it by design), and where the class needs a
+    transport field, protocol 1, 6 or 17 with the segment holding its header."""
+    seen = 0
+    for cid, f in seams.items():
+        P = f["P"]
+        for i, cl in f["planted"]:
+            if cl == "short_hdr":
+                continue
+            a, ln = int(P.starts[i]), int(P.ends[i] - P.starts[i])
+            hl, tl, proto = (int(P.buf[a]) & 15) * 4, (int(P.buf[a + 2]) << 8) | int(P.buf[a + 3]), int(P.buf[a + 9])
+            assert 20 <= hl <= tl <= ln, (cid, i, cl, hl, tl, ln)
+            if cl.startswith("l4field"):
+                assert proto in (1, 6, 17) and tl - hl >= {1: 4, 6: 20, 17: 8}[proto], (cid, i, cl, proto, tl - hl)
+            seen += 1
+    assert seen > 1000
+
+
+def test_the_class_counts_name_a_dropped_class():
+    """A generator that leaves one class out is named by the count check (not RAW's start@d: its 2-byte packets behind
+    one planted start make the next)."""
+    import seg_seams as S
+    for mode, kind, line128, drop in (("udp", "tx", False, "field@-1"), ("tx_datagram", "dg", False, "l4field@-2"),
+                                      ("verify_udp", "plain", False, "start@2"), ("tcp", "txw", True, "field@0")):
+        full = S.classes_for(kind, mode, line128)
+        b = S.batch(64, 4096, mode, line128, 0, [c for c in full if c != drop], 1537, np.random.default_rng(5))
+        offs = np.concatenate(([128], 128 + np.cumsum(b.lens)))
+        buf = np.zeros(int(offs[-1]), np.uint8)
+        if b.parts is not None:
+            buf[128:] = np.concatenate(b.parts)
+        got = S.missing(S.features(offs[:-1], offs[1:], 64, 4096, line128, mode, buf, data=128), full)
+        assert got and all(m.startswith(drop) for m in got), (drop, got)
+
+
+def seam_table(seams):
+    """Per k_seg key (kernel, in place, layout) over the seam cases: chunks, chunk ends on a
+    seam, interior packet starts on a seam, fields across a seam (TX: field@-1, DG: l4field@-1)."""
+    import seg_seams as S
+    rows = {}
+    for c in K.CASES[K.N_BEFORE_SEAMS:]:
+        ch, t, kind, line128 = seam_setup(c)
+        if K.is_seam(c):
+            counts, n = seams[c["id"]]["counts"], seams[c["id"]]["P"].n
+        else:
+            n = c["n"]
+            starts = c["base"] + c["stride"] * np.arange(n, dtype=np.int64)
+            counts = S.features(starts, starts + c["len"], ch, t, False, c["mode"], data=c["base"])
+        row = rows.setdefault((K.kernel_of(c)[0], c["fill"], c["layout"]), [0, 0, 0, 0, False])
+        both = lambda cl: counts[(cl, 0)] + counts[(cl, 1)]  # noqa: E731
+        row[0] += -(-n // ch)
+        row[1] += both("chunk_end@0")
+        row[2] += both("start@0")
+        row[3] += both("field@-1") + both("l4field@-1")
+        row[4] |= both("chunk_end@0") > 0 and both("start@0") > 0
+    return rows
+
+
+def test_every_k_seg_key_has_a_case_on_the_seams(seams, reachable):
+    """Every k_seg key the planner can reach, uniform ones included, has a case with a chunk
+    that ends on a seam and an interior packet that starts on one; the uniform TX shapes
+    put a field across a seam (in place: on one) in every chunk."""
+    import seg_seams as S
+    rows = seam_table(seams)
+    keys = {(k[0], k[3] == "1", k[4]) for k in reachable[0] if k[0].startswith("k_seg")}
+    assert keys == {k for k in case_keys_of_layouts() if k[0].startswith("k_seg")}
+    lacking = sorted(k for k in keys if not rows.get(k, [0, 0, 0, 0, False])[4])
+    assert not lacking, lacking
+    for k, row in sorted(rows.items()):
+        print("%-18s %-8s %s: %6d chunks, %6d chunk ends, %6d starts, %5d fields across a seam" % (
+            k[0], "in place" if k[1] else "", k[2], *row[:4]))
+    for c in K.CASES[K.N_BEFORE_SEAMS:]:
+        if c["layout"] == "U" and c["len"] in (141, 327, 431, 545, 272):
+            ch, t, _, _ = seam_setup(c)
+            starts = c["stride"] * np.arange(c["n"], dtype=np.int64)
+            f = S.features(starts, starts + c["len"], ch, t, False, c["mode"])
+            cl = "field@0" if c["fill"] else "field@-1"
+            assert f[(cl, 0)] + f[(cl, 1)] >= c["n"] // ch, (c["id"], f)
+
+
+def case_keys_of_layouts():
+    return {(K.kernel_of(c)[0], c["fill"], c["layout"]) for c in K.CASES}

@@ -1316,6 +1316,8 @@ __device__ __forceinline__ void seg_load(const BatchArgs &A, const SidePtrs &sp,
 // (the in-place writer's whole-line write-back, k_seg), unless that line begins
 // before the batch; else at its dword. The bytes in front are loaded but lie
 // before every point, and the line was fetched for the previous chunk anyway.
+// (tests/seg_seams.py geometry() is this rule's test-side twin: the ledger's seam
+// cases are planted with it, so a change of b0 here must change it there.)
 //
 // Out-of-contract chunks (device ragged batches, whose offsets the host never
 // reads): a packet whose offsets decrease or whose length exceeds lim, the
