@@ -69,14 +69,17 @@ extern "C" {
 /*  [mode]          mode is not 0 .. YU_MODE_COUNT-1 (every call); the   */
 /*                  scatter-gather device calls (yu_csum_*_iov): also   */
 /*                  IPV4, VERIFY_IPV4, VERIFY_RX and TX_DATAGRAM, which  */
-/*                  parse headers out of the packet.                     */
+/*                  parse headers out of the packet; the whole-datagram  */
+/*                  calls (yu_csum_*_iov_datagram) take those four and   */
+/*                  refuse every other mode.                             */
 /*  [out]           out == NULL in a yu_csum_batch_* call, or h_out ==   */
 /*                  NULL in a yu_csum_batch_host_* call, with n > 0 (the */
 /*                  fill calls take NULL: no result array; an empty     */
 /*                  batch, n == 0, is a no-op returning YU_OK).          */
 /*  [fill-mode]     a fill call (yu_csum_fill_*) with a mode that has no */
 /*                  field to write: RAW, VERIFY_* (or no mode at all);   */
-/*                  yu_csum_fill_iov: any mode but UDP, TCP and ICMP.    */
+/*                  yu_csum_fill_iov: any mode but UDP, TCP and ICMP;    */
+/*                  yu_csum_fill_iov_datagram: VERIFY_IPV4, VERIFY_RX.   */
 /*  [side-align]    device calls: initial_arr not 2-byte aligned, addrs  */
 /*                  not 4-byte aligned, out not 2-byte aligned.          */
 /*  [data]          data == NULL with n > 0 (device calls), h_data ==    */
@@ -388,8 +391,9 @@ int yu_csum_batch_host_iov(const yu_iovec *iov, const uint64_t *first_iov,
  * Modes: the whole-packet sums RAW, UDP, TCP, ICMP, VERIFY_TCP, VERIFY_UDP.
  * The TX modes take the checksum field as 0 wherever its two bytes lie, in two
  * different views included. IPV4, VERIFY_IPV4, VERIFY_RX and TX_DATAGRAM parse
- * headers out of the packet and are refused here with YU_EINVAL ([mode]; a
- * follow-up). The fill form takes UDP, TCP and ICMP ([fill-mode]).
+ * headers out of the packet and are refused here with YU_EINVAL ([mode]):
+ * yu_csum_batch_iov_datagram / yu_csum_fill_iov_datagram below take them. The
+ * fill form takes UDP, TCP and ICMP ([fill-mode]).
  *
  * Views: any base address, any length (odd ones included), any number per
  * packet (0 included), in any address order, in any number of allocations. A
@@ -423,6 +427,53 @@ int yu_csum_fill_iov(const yu_iovec *views, const uint64_t *first_iov,
                      uint64_t n, int mode, const uint16_t *initial_arr,
                      uint16_t initial, const uint8_t *addrs, uint16_t *out,
                      void *stream);
+
+/* Scatter-gather device batches of whole IPv4 datagrams: the four modes that
+ * parse headers out of the packet, on the layout and call discipline of
+ * yu_csum_batch_iov above (device CSR tables and bases, asynchronous on
+ * `stream`, no allocation, no synchronisation, graph-capturable, YU_ENODEV
+ * without a device, n == 0 a no-op returning YU_OK after the mode checks). A
+ * received burst held as views is verified where it lies (VERIFY_RX), and an
+ * outgoing datagram held as header view + payload view gets both of its fields
+ * in one pass (TX_DATAGRAM). Every input is read from the datagram, so there
+ * are no side arrays.
+ *
+ * Modes: IPV4, VERIFY_IPV4, VERIFY_RX, TX_DATAGRAM; every other mode is [mode]
+ * (yu_csum_batch_iov takes those). The fill form takes IPV4 and TX_DATAGRAM
+ * ([fill-mode]). `out` holds n * YU_MODE_OUTPUTS(mode) values and may be NULL
+ * in the fill form.
+ *
+ * Value: out is exactly what yu_csum_batch_ragged returns for the same bytes
+ * laid back to back, in every case that form defines: packets shorter than 20
+ * bytes (0 included), any IHL (VERIFY_RX accepts HeaderLength() < 20,
+ * TX_DATAGRAM answers {0, 0}), TotalLength() below, at or past the bytes
+ * present, bytes past TotalLength() (left out of the transport sum), protocols
+ * other than 1, 6 and 17, segments shorter than their fixed header. The header
+ * may lie in any number of views, one-byte and empty ones included.
+ *
+ * Fill: exactly the fields yu_csum_fill_ragged stores. IPV4: bytes 10..11 iff
+ * min(len, IHL*4) >= 12. TX_DATAGRAM: bytes 10..11 iff len >= 20 and 20 <=
+ * HeaderLength() <= TotalLength() <= len, then the transport field at
+ * HeaderLength() + {6 UDP, 16 TCP, 2 ICMP} iff the segment holds its fixed
+ * header (8 / 20 / 4 bytes). Each field is stored through the views as
+ * yu_csum_fill_iov stores its field: one 16-bit store when its two bytes are
+ * adjacent in memory at an even address, two byte stores otherwise (two views
+ * included). Nothing else is written.
+ *
+ * Views, length and "out of contract" are those of yu_csum_batch_iov: at most
+ * YU_MAX_TRANSPORT_LEN bytes per packet; an over-limit packet, or one at which
+ * first_iov decreases, gets an unspecified value and no field store, never a
+ * fault or a hang, and every other packet stays exact. A call reads only
+ * dwords that hold bytes of views it names: IPV4 and VERIFY_IPV4 only those of
+ * the packet's first min(60, len) bytes, VERIFY_RX and TX_DATAGRAM those and
+ * the bytes [HeaderLength(), TotalLength()) of a datagram they sum.
+ *
+ * YU_EINVAL (Preconditions above): [mode], [fill-mode], [out], [side-align]
+ * (out), [offsets], [data], as for yu_csum_batch_iov. */
+int yu_csum_batch_iov_datagram(const yu_iovec *views, const uint64_t *first_iov,
+                               uint64_t n, int mode, uint16_t *out, void *stream);
+int yu_csum_fill_iov_datagram(const yu_iovec *views, const uint64_t *first_iov,
+                              uint64_t n, int mode, uint16_t *out, void *stream);
 
 /* Host-memory field writer: the matching yu_csum_batch_host_* call (TX modes
  * UDP/TCP/IPV4/ICMP/TX_DATAGRAM only), then each result stored big-endian into the
@@ -555,6 +606,8 @@ const char *yu_ragged_fill_variant_n(int mode, uint64_t n);
  * packets (fill != 0: yu_csum_fill_iov); "" for a mode the form refuses. No
  * device needed. */
 const char *yu_iov_variant_n(int mode, uint64_t n, int fill);
+/* The same for the whole-datagram calls (fill != 0: yu_csum_fill_iov_datagram). */
+const char *yu_iov_datagram_variant_n(int mode, uint64_t n, int fill);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,8 @@
 
 Thin Python front end over the C ABI's batched entry points
 (``yu_csum_batch_uniform`` / ``yu_csum_batch_ragged`` / ``yu_csum_batch_iov`` /
-``yu_csum_fill_*`` / ``yu_csum_batch_host_uniform``, include/yucsum.h). PyTorch is used only for device
+``yu_csum_batch_iov_datagram`` / ``yu_csum_fill_*`` / ``yu_csum_batch_host_uniform``,
+include/yucsum.h). PyTorch is used only for device
 memory and streams: the arithmetic happens in the hand-written gfx950 kernels of
 ``csrc/yucsum_kernels.hip``. There is no CPU fallback — without a HIP device every
 entry point raises :class:`yustack_amd._lib.YuError`.
@@ -169,33 +170,10 @@ def _dev_index(t, name: str, device, numel: int | None = None) -> torch.Tensor:
     return (t.view(torch.int64) if t.dtype == torch.uint64 else t.to(torch.int64)).contiguous()
 
 
-def checksum_iov(pools, view_pool: torch.Tensor, view_off: torch.Tensor, view_len: torch.Tensor,
-                 first: torch.Tensor, mode="raw", *, initial: int = 0,
-                 initial_arr: torch.Tensor | None = None, addrs: torch.Tensor | None = None,
-                 out: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None,
-                 fill: bool = False, validate: bool = True) -> torch.Tensor:
-    """Per-packet sums of scatter-gather device packets (yu_csum_batch_iov /
-    yu_csum_fill_iov): view j is ``pools[view_pool[j]][view_off[j] : view_off[j] + view_len[j]]``
-    and packet i the concatenation of views ``first[i] .. first[i+1]-1`` (``first``: n+1
-    non-decreasing entries), e.g. a header pool and a payload pool. ``pools`` is a
-    list of contiguous uint8 CUDA tensors on one device; the view arrays and
-    ``first`` are CUDA integer tensors there. Each result is what
-    :func:`checksum_ragged` gives for the same bytes laid back to back. Modes: RAW,
-    UDP, TCP, ICMP, VERIFY_TCP, VERIFY_UDP; packets of at most 65535 bytes.
-    ``fill=True`` (UDP, TCP, ICMP) also stores each result big-endian into the
-    packet's checksum field where it lies in the pools, across two views if need be.
-
-    The device ``yu_iovec`` table is built with torch operations (no host loop
-    over views; capturable in a graph with ``validate=False``). ``validate`` checks
-    on the device that every view lies inside its pool, that ``first`` is
-    non-decreasing within the view count and that no packet is longer than 65535
-    bytes (one small synchronisation). The returned tensor holds the table
-    (``out.iov_table``), which must outlive the enqueued call."""
-    m = _mode(mode)
-    if m not in IOV_MODES:
-        raise ValueError("checksum_iov takes the whole-packet modes: raw, udp, tcp, icmp, verify_tcp, verify_udp")
-    if fill and m not in IOV_FILL_MODES:
-        raise ValueError("fill=True takes udp, tcp or icmp")
+def _iov_table(pools, view_pool, view_off, view_len, first, validate: bool):
+    """The device ``yu_iovec`` table of the scatter-gather calls, built with torch
+    operations, and the checks ``validate`` asks for. Returns (device, table, first
+    as int64, n)."""
     pools = list(pools)
     if not pools:
         raise ValueError("pools must hold at least one tensor")
@@ -236,24 +214,99 @@ def checksum_iov(pools, view_pool: torch.Tensor, view_off: torch.Tensor, view_le
             raise ValueError("scatter-gather packets must be <= 65535 bytes")
     table = torch.stack((base, vl), dim=1).contiguous() if nviews else \
         torch.zeros((1, 2), dtype=torch.int64, device=dev)
+    return dev, table, fi, n
+
+
+def _iov_call(name: str, dev, table, fi, stream, call):
+    """Enqueues one scatter-gather call on ``stream`` (the table was built on the
+    current stream)."""
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream(dev))
+        table.record_stream(stream)
+        fi.record_stream(stream)
+    with torch.cuda.device(dev):
+        rc = call(getattr(lib(), name), _stream(dev, stream))
+    check(rc, name)
+
+
+def checksum_iov(pools, view_pool: torch.Tensor, view_off: torch.Tensor, view_len: torch.Tensor,
+                 first: torch.Tensor, mode="raw", *, initial: int = 0,
+                 initial_arr: torch.Tensor | None = None, addrs: torch.Tensor | None = None,
+                 out: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None,
+                 fill: bool = False, validate: bool = True) -> torch.Tensor:
+    """Per-packet sums of scatter-gather device packets (yu_csum_batch_iov /
+    yu_csum_fill_iov): view j is ``pools[view_pool[j]][view_off[j] : view_off[j] + view_len[j]]``
+    and packet i the concatenation of views ``first[i] .. first[i+1]-1`` (``first``: n+1
+    non-decreasing entries), e.g. a header pool and a payload pool. ``pools`` is a
+    list of contiguous uint8 CUDA tensors on one device; the view arrays and
+    ``first`` are CUDA integer tensors there. Each result is what
+    :func:`checksum_ragged` gives for the same bytes laid back to back. Modes: RAW,
+    UDP, TCP, ICMP, VERIFY_TCP, VERIFY_UDP; packets of at most 65535 bytes.
+    ``fill=True`` (UDP, TCP, ICMP) also stores each result big-endian into the
+    packet's checksum field where it lies in the pools, across two views if need be.
+
+    The device ``yu_iovec`` table is built with torch operations (no host loop
+    over views; capturable in a graph with ``validate=False``). ``validate`` checks
+    on the device that every view lies inside its pool, that ``first`` is
+    non-decreasing within the view count and that no packet is longer than 65535
+    bytes (one small synchronisation). The returned tensor holds the table
+    (``out.iov_table``), which must outlive the enqueued call."""
+    m = _mode(mode)
+    if m not in IOV_MODES:
+        raise ValueError("checksum_iov takes the whole-packet modes: raw, udp, tcp, icmp, verify_tcp, verify_udp")
+    if fill and m not in IOV_FILL_MODES:
+        raise ValueError("fill=True takes udp, tcp or icmp")
+    dev, table, fi, n = _iov_table(pools, view_pool, view_off, view_len, first, validate)
     initial_arr = _opt(initial_arr, torch.uint16, n, dev, "initial_arr")
     addrs = _opt(addrs, torch.uint8, 8 * n, dev, "addrs")
     if out is None:
         out = torch.empty(max(n, 1), dtype=torch.uint16, device=dev)[:n]
     else:
         _opt(out, torch.uint16, n, dev, "out")
-    if stream is not None:  # the table was built on the current stream
-        stream.wait_stream(torch.cuda.current_stream(dev))
-        table.record_stream(stream)
-        fi.record_stream(stream)
-    with torch.cuda.device(dev):
-        name = "yu_csum_fill_iov" if fill else "yu_csum_batch_iov"
-        rc = getattr(lib(), name)(table.data_ptr(), fi.data_ptr(), n, m, _ptr(initial_arr),
-                                  initial & 0xFFFF, _ptr(addrs), out.data_ptr() if n else None,
-                                  _stream(dev, stream))
-    check(rc, name)
+    _iov_call("yu_csum_fill_iov" if fill else "yu_csum_batch_iov", dev, table, fi, stream,
+              lambda f, s: f(table.data_ptr(), fi.data_ptr(), n, m, _ptr(initial_arr), initial & 0xFFFF,
+                             _ptr(addrs), out.data_ptr() if n else None, s))
     out.iov_table = (table, fi)
     return out
+
+
+IOV_DATAGRAM_MODES = (IPV4, VERIFY_IPV4, VERIFY_RX, TX_DATAGRAM)
+IOV_DATAGRAM_FILL_MODES = (IPV4, TX_DATAGRAM)
+
+
+def checksum_iov_datagrams(pools, view_pool: torch.Tensor, view_off: torch.Tensor, view_len: torch.Tensor,
+                           first: torch.Tensor, mode="verify_rx", *, out: torch.Tensor | None = None,
+                           stream: torch.cuda.Stream | None = None, fill: bool = False,
+                           validate: bool = True) -> torch.Tensor:
+    """Whole IPv4 datagrams held as scatter-gather device packets
+    (yu_csum_batch_iov_datagram / yu_csum_fill_iov_datagram): the layout, the table,
+    ``validate``, ``stream`` and ``out.iov_table`` are :func:`checksum_iov`'s. Modes:
+    IPV4, VERIFY_IPV4, VERIFY_RX, TX_DATAGRAM, whose inputs are read from each
+    datagram, so there are no side arrays. Returns ``n * outputs(mode)`` uint16
+    results, each what :func:`checksum_ragged` gives for the same bytes laid back to
+    back. ``fill=True`` (IPV4, TX_DATAGRAM) also stores the fields
+    :func:`checksum_ragged` stores, where they lie in the pools."""
+    m = _mode(mode)
+    if m not in IOV_DATAGRAM_MODES:
+        raise ValueError("checksum_iov_datagrams takes ipv4, verify_ipv4, verify_rx and tx_datagram")
+    if fill and m not in IOV_DATAGRAM_FILL_MODES:
+        raise ValueError("fill=True takes ipv4 or tx_datagram")
+    dev, table, fi, n = _iov_table(pools, view_pool, view_off, view_len, first, validate)
+    k = outputs(m)
+    if out is None:
+        out = torch.empty(max(n * k, 1), dtype=torch.uint16, device=dev)[:n * k]
+    else:
+        _opt(out, torch.uint16, n * k, dev, "out")
+    _iov_call("yu_csum_fill_iov_datagram" if fill else "yu_csum_batch_iov_datagram", dev, table, fi, stream,
+              lambda f, s: f(table.data_ptr(), fi.data_ptr(), n, m, out.data_ptr() if n else None, s))
+    out.iov_table = (table, fi)
+    return out
+
+
+def iov_datagram_variant(mode="verify_rx", n: int = 1 << 20, fill: bool = False) -> str:
+    """Name of the kernel the whole-datagram scatter-gather calls launch ("" for a
+    mode they refuse)."""
+    return lib().yu_iov_datagram_variant_n(_mode(mode), n, 1 if fill else 0).decode()
 
 
 def iov_variant(mode="raw", n: int = 1 << 20, fill: bool = False) -> str:

@@ -27,8 +27,12 @@
 // is found by the walk; its bytes are read out of the registers holding them
 // and taken off the sum of their view's class, exactly, before folding.
 //
-// No HIP call is made here: the kernel and tests/cpp/iov_combine.cpp both use
-// these functions.
+// The kernel's whole-datagram kind (yu_csum_batch_iov_datagram /
+// yu_csum_fill_iov_datagram) adds a header gather, a parse and a window to the
+// walk: the last section of this file.
+//
+// No HIP call is made here: the kernel and tests/cpp/iov_combine.cpp (the
+// datagram kind: tests/cpp/iov_datagram.cpp) both use these functions.
 #ifndef YUCSUM_IOV_H
 #define YUCSUM_IOV_H
 
@@ -210,6 +214,136 @@ YU_IOV_FN uint32_t iov_value(int mode, uint32_t v, uint32_t len, bool have_addrs
 YU_IOV_FN bool iov_mode_ok(int m) { return m == 0 || m == 1 || m == 2 || m == 4 || m == 6 || m == 7; }
 YU_IOV_FN bool iov_mode_tx(int m) { return m == 1 || m == 2 || m == 4; }
 YU_IOV_FN uint32_t iov_mode_field(int m) { return m == 1 ? 6u : (m == 2 ? 16u : (m == 4 ? 2u : 0u)); }
+
+// ---------------------------------------------------------------------
+// Whole IPv4 datagrams (yu_csum_batch_iov_datagram / yu_csum_fill_iov_datagram):
+// IPV4, VERIFY_IPV4, VERIFY_RX and TX_DATAGRAM parse the header out of the
+// packet. Lane j < 60 of the wave holds packet byte j (a byte load from the view
+// that holds it, issued a packet ahead); the parse reads bytes 0, 2, 3 and 9,
+// the IPv4 header's big-endian sum over b[:min(HL, len)] and the pseudo
+// header's over bytes 12..19 are sums over the lanes (iov_dg_term: byte j weighs
+// 256 when j is even), and the transport segment is the walk above with a
+// window: of each view only the bytes at packet offsets [HL, TL) are cut into
+// slots. HL is a multiple of 4, so a byte's class (address parity XOR its
+// offset in the packet) is its class in the segment, and the transport field
+// is the field mechanism above at f = HL + {6 UDP, 16 TCP, 2 ICMP}. The
+// segment's sum is a sum of its own bytes only, never a difference of
+// residues, so it is 0 exactly when every byte of it is zero.
+// ---------------------------------------------------------------------
+constexpr uint32_t kIovHdr = 60u;  // header bytes the lanes gather: IHL <= 15
+
+YU_IOV_FN bool iov_dg_mode_ok(int m) { return m == 3 || m == 5 || m == 8 || m == 9; }  // IPV4, VERIFY_IPV4, VERIFY_RX, TX_DATAGRAM
+YU_IOV_FN bool iov_dg_mode_tx(int m) { return m == 3 || m == 9; }                       // the two that store fields
+
+// What the parse of a packet's first bytes fixes before its walk starts.
+struct IovDg {
+  uint32_t lo, hi;  // the walk's window of packet offsets (lo == hi: nothing is summed)
+  uint32_t f;       // TX_DATAGRAM: the transport field's packet offset (0: none)
+  uint32_t tl;      // TotalLength()
+  uint32_t meta;    // HL | bytes of the header sum << 6 | Protocol() << 12 | kIovDgOk | kIovDgL4
+};
+constexpr uint32_t kIovDgOk = 1u << 20;  // len >= 20 and HL <= TL (TX_DATAGRAM: and HL >= 20); TL <= len is known after the walk
+constexpr uint32_t kIovDgL4 = 1u << 21;  // ... and the protocol is TCP, UDP or ICMP
+YU_IOV_FN uint32_t iov_dg_hl(uint32_t meta) { return meta & 63u; }
+YU_IOV_FN uint32_t iov_dg_hn(uint32_t meta) { return (meta >> 6) & 63u; }
+YU_IOV_FN uint32_t iov_dg_proto(uint32_t meta) { return (meta >> 12) & 0xFFu; }
+
+// have = min(len, kIovHdr); b0, b2, b3, b9: packet bytes 0, 2, 3, 9 (anything
+// where the packet is shorter).
+YU_IOV_FN void iov_dg_parse(IovDg &D, int mode, uint32_t have, uint32_t b0, uint32_t b2, uint32_t b3,
+                            uint32_t b9) {
+  const uint32_t hl = have ? (b0 & 15u) * 4u : 0u;      // HeaderLength()
+  const uint32_t hn = hl < have ? hl : have;            // b[:IHL*4], clamped to the packet
+  const uint32_t tl = ((b2 & 0xFFu) << 8) | (b3 & 0xFFu);
+  const uint32_t proto = b9 & 0xFFu;
+  const bool walk = mode == 8 || mode == 9;
+  const bool ok = have >= 20u && hl <= tl && (mode != 9 || hl >= 20u);
+  const bool l4 = ok && (proto == 6u || proto == 17u || proto == 1u);
+  uint32_t lo = 0, hi = 0, f = 0;
+  if (walk && l4) {
+    lo = hl;
+    hi = tl;
+    if (mode == 9) {  // the field exists when the segment holds its fixed header
+      const uint32_t fo = proto == 17u ? 6u : (proto == 6u ? 16u : 2u);
+      const uint32_t mn = proto == 17u ? 8u : (proto == 6u ? 20u : 4u);
+      if (tl - hl >= mn) f = hl + fo; else hi = lo;
+    }
+  }
+  D.lo = lo;
+  D.hi = hi;
+  D.f = f;
+  D.tl = tl;
+  D.meta = hl | (hn << 6) | (proto << 12) | (ok ? kIovDgOk : 0u) | (l4 ? kIovDgL4 : 0u);
+}
+
+// What packet byte j (lane j) adds to a big-endian sum that starts at an even offset.
+YU_IOV_FN uint32_t iov_dg_term(uint32_t j, uint32_t byte) { return (j & 1u) ? (byte & 0xFFu) : ((byte & 0xFFu) << 8); }
+// Lane j's share of the IPv4 header's sum (field bytes 10, 11 taken as zero in
+// the modes that store them, when the summed bytes hold both: of an 11-byte
+// packet byte 10 is summed as it is) and of the pseudo header's {src, dst}.
+YU_IOV_FN uint32_t iov_dg_hdr_term(uint32_t meta, int mode, uint32_t j, uint32_t byte) {
+  const bool fld = iov_dg_mode_tx(mode) && iov_dg_hn(meta) >= 12u && (j == 10u || j == 11u);
+  return j < iov_dg_hn(meta) && !fld ? iov_dg_term(j, byte) : 0u;
+}
+YU_IOV_FN uint32_t iov_dg_pseudo_term(uint32_t j, uint32_t byte) {
+  return j >= 12u && j < 20u ? iov_dg_term(j, byte) : 0u;
+}
+
+// iov_walk_view with the window [lo, hi) of packet offsets: of the view's bytes
+// only those inside it are cut into slots (none: the view is done at once and
+// costs no slot); W.off and W.over count the whole view as ever.
+YU_IOV_FN void iov_walk_view_win(IovWalk &W, uint64_t addr, uint64_t len, uint32_t lo, uint32_t hi,
+                                 bool tx, uint32_t f) {
+  const uint32_t off = W.off, room = kIovLimit - off;
+  const uint32_t take = len <= room ? (uint32_t)len : room;
+  const uint32_t over = W.over | (len > room ? 1u : 0u);
+  const uint32_t end = off + take;
+  const uint32_t a = off > lo ? off : lo, b = end < hi ? end : hi;
+  const bool in = a < b;
+  W.off = in ? a : off;
+  iov_walk_view(W, in ? addr + (a - off) : addr, in ? b - a : 0u, tx, f);
+  W.off = end;
+  W.over = over;
+}
+
+// The epilogue. len: the packet's bytes; hs, ps: the lanes' header and pseudo
+// sums; (sA, sB): the window's class sums, the field's bytes taken off. r0 / r1:
+// the results (r1: TX_DATAGRAM's transport value); st0 / st1: whether the fill
+// form stores the field (bytes 10..11 / the transport field at D.f).
+YU_IOV_FN void iov_dg_value(const IovDg &D, int mode, uint32_t len, uint32_t hs, uint32_t ps, uint32_t sA,
+                            uint32_t sB, uint32_t &r0, uint32_t &r1, bool &st0, bool &st1) {
+  const uint32_t meta = D.meta, hl = iov_dg_hl(meta), proto = iov_dg_proto(meta);
+  const uint32_t ip = iov_fold(hs);
+  const bool valid = (meta & kIovDgOk) && D.tl <= len;
+  uint32_t seg = iov_residue(sA, sB);
+  if (proto != 1u) seg += ps + proto + ((D.tl - hl) & 0xFFFFu);  // ICMP has no pseudo header
+  seg = iov_fold(seg);
+  r0 = r1 = 0;
+  st0 = st1 = false;
+  if (mode == 5) {  // VERIFY_IPV4
+    r0 = ip;
+  } else if (mode == 3) {  // IPV4
+    r0 = (~ip) & 0xFFFFu;
+    st0 = iov_dg_hn(meta) >= 12u;
+  } else if (mode == 8) {  // VERIFY_RX
+    if (!valid) {
+      r0 = 8u;  // YU_RX_INVALID
+    } else {
+      if (ip == 0u || ip == 0xFFFFu) r0 |= 1u;  // YU_RX_IP_OK
+      if (meta & kIovDgL4) {
+        r0 |= 2u;                                     // YU_RX_L4
+        if (seg == 0u || seg == 0xFFFFu) r0 |= 4u;    // YU_RX_L4_OK
+      }
+    }
+  } else if (valid) {  // TX_DATAGRAM
+    r0 = (~ip) & 0xFFFFu;
+    st0 = true;
+    if (D.f) {
+      r1 = (~seg) & 0xFFFFu;
+      st1 = true;
+    }
+  }
+}
 
 }  // namespace yu
 #pragma GCC visibility pop

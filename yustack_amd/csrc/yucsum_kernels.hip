@@ -70,9 +70,11 @@
 //     and ragged: one lane per packet, 32-byte reads.
 //   k_loop<U, BE> / k_loop_rx<U>: one wave per packet, for ragged bursts of up
 //     to 4096 packets and for few or sparse uniform packets > 4 KiB.
-//   k_iov<U, NT, FILL>: scatter-gather packets (yu_csum_batch_iov / yu_csum_fill_iov,
+//   k_iov<U, NT, FILL, DG>: scatter-gather packets (yu_csum_batch_iov / yu_csum_fill_iov,
 //     planned by yu::plan_iov): one wave per packet walking its views, each step U
-//     load slots of 1 KiB of whichever view comes next (yucsum_iov.h).
+//     load slots of 1 KiB of whichever view comes next (yucsum_iov.h). DG: whole IPv4
+//     datagrams (yu_csum_batch_iov_datagram / yu_csum_fill_iov_datagram): the header
+//     gathered into the lanes a packet ahead, the walk windowed to [HL, TL).
 //   All are grid-stride kernels; the grid is sized per CU and over-subscribed
 //   (see blocks_per_cu in yucsum_plan.cpp), except that k_seg narrows it for
 //   small packets (seg_waves).
@@ -1548,6 +1550,17 @@ __device__ __forceinline__ void put_be16(uint8_t *q, uint32_t r) {
   }
 }
 
+// The same for a field whose two bytes have an address each (they may lie in
+// two views): one 16-bit store when they are adjacent at an even address.
+__device__ __forceinline__ void put_be16_at(uint8_t *q0, uint8_t *q1, uint32_t r) {
+  if (q1 == q0 + 1 && ((uintptr_t)q0 & 1u) == 0) {
+    *(uint16_t *)q0 = (uint16_t)(((r >> 8) | (r << 8)) & 0xFFFFu);
+  } else {
+    *q0 = (uint8_t)(r >> 8);
+    *q1 = (uint8_t)r;
+  }
+}
+
 // Parse the gathered header of a packet of length len starting sh = start&3
 // bytes into h[0] (header/ipv4.go:91-118,126-138). Returns the header and
 // total lengths through hl/tl.
@@ -2180,8 +2193,10 @@ __global__ __launch_bounds__(256) void k_loop_rx(BatchArgs A) {
 }
 
 // ---------------------------------------------------------------------
-// k_iov<U, NT, FILL>: scatter-gather packets (yu_csum_batch_iov /
-// yu_csum_fill_iov), one wave per packet. The arithmetic, the walk over a
+// k_iov<U, NT, FILL, DG>: scatter-gather packets (yu_csum_batch_iov /
+// yu_csum_fill_iov; DG: yu_csum_batch_iov_datagram / yu_csum_fill_iov_datagram,
+// whole IPv4 datagrams whose header is parsed out of the packet, see the end
+// of this comment), one wave per packet. The arithmetic, the walk over a
 // packet's views and the load slots it cuts them into are yucsum_iov.h's; a
 // step here is U slots, so a 2-view MTU packet (header view, payload view) is
 // one step. The loads of the next step (of this packet or the next) are issued
@@ -2197,6 +2212,12 @@ __global__ __launch_bounds__(256) void k_loop_rx(BatchArgs A) {
 // call (out, the fields) may touch the tables.
 // NT: 0 plain loads, 1 nt, 2 plain for a step's first slot (a short header
 // view, whose line its neighbours share) and nt for the rest.
+// DG (IPV4, VERIFY_IPV4, VERIFY_RX, TX_DATAGRAM): lane j < 60 also loads packet
+// byte j, a packet ahead of the walk, so the records run two packets ahead and
+// first_iov three. When the walk reaches the packet its header is parsed from
+// those lanes, the header and pseudo-header sums are taken over them, and the
+// walk gets the window [HL, TL) and the packet's own field offset (yucsum_iov.h).
+// The header-only modes get an empty window: their walk only counts the bytes.
 // ---------------------------------------------------------------------
 #define YU_CONST_AS __attribute__((address_space(4)))
 template <typename T>
@@ -2218,6 +2239,10 @@ struct IovPkt {
   uint32_t nv;      // its views (0 when first_iov decreases: out of contract)
   uint32_t blo, bhi, len;  // lane k: view g0 + k (a length past 32 bits is past every limit: clamped)
   uint32_t sa, sb, si;     // lead lane: the {src, dst} record; initial_arr's entry or the scalar initial
+  // DG: lane j < have holds packet byte j, loaded from address ga
+  uint32_t have;           // min(len, yu::kIovHdr)
+  uint32_t hb;
+  uint64_t ga;
 };
 
 // What finishing a packet needs, taken when the walk leaves it. Only the lead
@@ -2227,9 +2252,12 @@ struct IovFin {
   uint32_t len;  // the packet's bytes; bit 31: out of contract, no field store
   uint64_t fp0, fp1;
   uint32_t sa, sb, si;
+  // DG: the parsed header (yu::IovDg), its sums and the addresses of bytes 10 and 11
+  uint32_t tl, meta, f, hs, ps;
+  uint64_t ip0, ip1;
 };
 
-template <int U, int NT, bool FILL>
+template <int U, int NT, bool FILL, bool DG = false>
 __global__ __launch_bounds__(256) void k_iov(const yu_iovec *views_, const uint64_t *first_,
                                              const uint16_t *initial_arr, const uint8_t *addrs_,
                                              IovArgs A) {
@@ -2240,9 +2268,9 @@ __global__ __launch_bounds__(256) void k_iov(const yu_iovec *views_, const uint6
   const uint64_t wave = grid_wave(0u);
   const uint64_t nwave = (uint64_t)gridDim.x * (blockDim.x >> 6);
   const int mode = A.mode;
-  const uint32_t f = yu::iov_mode_field(mode);
+  const uint32_t f = DG ? 0u : yu::iov_mode_field(mode);
   const bool tx = f != 0;  // == yu::iov_mode_tx(mode)
-  const uint8_t *addrs = mode_has_pseudo(mode) ? addrs_ : nullptr;
+  const uint8_t *addrs = !DG && mode_has_pseudo(mode) ? addrs_ : nullptr;
   if (wave >= A.n) return;
 
   // first_iov[q], first_iov[q + 1] of packet q (none: an empty packet)
@@ -2265,6 +2293,10 @@ __global__ __launch_bounds__(256) void k_iov(const yu_iovec *views_, const uint6
     P.blo = v.x;
     P.bhi = v.y;
     P.len = v.w ? 0xFFFFFFFFu : v.z;
+    P.have = P.hb = 0u;
+    P.ga = 0ull;
+    P.sa = P.sb = P.si = 0u;
+    if constexpr (DG) return;  // no side arrays: the datagram carries its own
     // the packet's side data, by the lead lane alone (an absent array: nothing)
     const uint32_t own = lead && q < A.n ? 0u : kOOB;
     const uint64_t ab = uniform64(addrs ? (uint64_t)(uintptr_t)(addrs + 8 * q) : 0ull);
@@ -2281,10 +2313,52 @@ __global__ __launch_bounds__(256) void k_iov(const yu_iovec *views_, const uint6
     P.si = initial_arr ? (uint32_t)sin : A.initial;
   };
 
+  // View k of packet P for the gather: a record the lanes hold, or one read as it
+  // is needed (next_view's own copy of this is left as it was: through this
+  // lambda the whole-packet instantiations compile to other code).
+  auto record = [&](const IovPkt &P, uint32_t k, uint64_t &b, uint32_t &l) __attribute__((always_inline)) {
+    if (k < 64u) {
+      b = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)P.bhi, (int)k) << 32) |
+          (uint32_t)__builtin_amdgcn_readlane((int)P.blo, (int)k);
+      l = (uint32_t)__builtin_amdgcn_readlane((int)P.len, (int)k);
+    } else {  // past the records the lanes hold
+      const uint64_t vl = views[P.g0 + k].len;
+      b = (uint64_t)(uintptr_t)views[P.g0 + k].base;
+      l = vl < 0xFFFFFFFFull ? (uint32_t)vl : 0xFFFFFFFFu;
+    }
+  };
+  // DG: the header gather of packet P, whose records have arrived. The views are
+  // taken in order until they hold kIovHdr bytes (a wave-uniform loop without a
+  // load but for records past the 64th); lane j takes the address of packet byte
+  // j and loads it. Lanes past the packet's bytes load its byte 0 again, so the
+  // load is unconditional for the lanes and touches nothing the packet does not
+  // hold; a packet without a byte loads nothing (a wave-uniform branch).
+  auto gather = [&](IovPkt &P) __attribute__((always_inline)) {
+    uint32_t off = 0, k = 0;
+    uint64_t ga = 0, a0 = 0;
+    while (off < yu::kIovHdr && k < P.nv) {
+      uint64_t b;
+      uint32_t l;
+      record(P, k, b, l);
+      l = l < 0x10000u ? l : 0x10000u;  // past every limit; keeps lane - off < l exact
+      if (off == 0u) a0 = b;
+      if (lane - off < l) ga = b + (lane - off);  // off <= lane < off + l
+      off += l;
+      ++k;
+    }
+    const uint32_t have = off < yu::kIovHdr ? off : yu::kIovHdr;
+    P.have = have;
+    P.ga = lane < have ? ga : a0;
+    P.hb = 0u;
+    if (have) P.hb = *(const __attribute__((address_space(1))) uint8_t *)(uintptr_t)P.ga;
+  };
+
   // The walk: packet wp, view vi of it; nx: packet wp + nwave; (ff0, ff1):
-  // first_iov of packet wp + 2 nwave.
+  // first_iov of packet wp + 2 nwave. DG: nx's header bytes are on their way too,
+  // so the records run two packets ahead (nn: packet wp + 2 nwave) and first_iov
+  // three.
   uint64_t wp = wave, ff0, ff1;
-  IovPkt cur, nx;
+  IovPkt cur, nx, nn;
   {
     uint64_t a0, a1, b0, b1;
     first_pair(wp, a0, a1);
@@ -2292,10 +2366,28 @@ __global__ __launch_bounds__(256) void k_iov(const yu_iovec *views_, const uint6
     first_pair(wp + 2 * nwave, ff0, ff1);
     packet(cur, wp, a0, a1);
     packet(nx, wp + nwave, b0, b1);
+    if constexpr (DG) {
+      packet(nn, wp + 2 * nwave, ff0, ff1);
+      first_pair(wp + 3 * nwave, ff0, ff1);
+      gather(cur);
+      gather(nx);
+    }
   }
   yu::IovWalk W;
   yu::iov_walk_reset(W);
   uint32_t vi = 0;
+  // DG: the current packet's parsed header and, in the lead lane, its sums
+  yu::IovDg D = {0u, 0u, 0u, 0u, 0u};
+  uint32_t dhs = 0, dps = 0;
+  auto parse = [&]() __attribute__((always_inline)) {
+    const int hb = (int)cur.hb;
+    yu::iov_dg_parse(D, mode, cur.have, (uint32_t)__builtin_amdgcn_readlane(hb, 0),
+                     (uint32_t)__builtin_amdgcn_readlane(hb, 2), (uint32_t)__builtin_amdgcn_readlane(hb, 3),
+                     (uint32_t)__builtin_amdgcn_readlane(hb, 9));
+    dhs = group_total<64>(yu::iov_dg_hdr_term(D.meta, mode, lane, cur.hb));
+    dps = group_total<64>(yu::iov_dg_pseudo_term(lane, cur.hb));
+  };
+  if constexpr (DG) parse();
 
   // Makes the walk's current view one with bytes left, if the packet has one.
   auto next_view = [&]() __attribute__((always_inline)) {
@@ -2311,7 +2403,11 @@ __global__ __launch_bounds__(256) void k_iov(const yu_iovec *views_, const uint6
         b = (uint64_t)(uintptr_t)views[cur.g0 + vi].base;
         l = vl < 0xFFFFFFFFull ? (uint32_t)vl : 0xFFFFFFFFu;
       }
-      yu::iov_walk_view(W, b, l, tx, f);
+      if constexpr (DG) {
+        yu::iov_walk_view_win(W, b, l, D.lo, D.hi, D.f != 0u, D.f);
+      } else {
+        yu::iov_walk_view(W, b, l, tx, f);
+      }
       ++vi;
     }
   };
@@ -2340,10 +2436,27 @@ __global__ __launch_bounds__(256) void k_iov(const yu_iovec *views_, const uint6
       fin.sa = cur.sa;
       fin.sb = cur.sb;
       fin.si = cur.si;
+      if constexpr (DG) {
+        fin.tl = lead ? D.tl : 0u;
+        fin.meta = lead ? D.meta : 0u;
+        fin.f = lead ? D.f : 0u;
+        fin.hs = dhs;
+        fin.ps = dps;
+        fin.ip0 = lead ? readlane64(cur.ga, 10u) : 0ull;
+        fin.ip1 = lead ? readlane64(cur.ga, 11u) : 0ull;
+      }
       wp += nwave;
       cur = nx;
-      packet(nx, wp + nwave, ff0, ff1);
-      first_pair(wp + 2 * nwave, ff0, ff1);
+      if constexpr (DG) {  // nx's records came a packet ago: its header bytes set off now
+        nx = nn;
+        gather(nx);
+        packet(nn, wp + 2 * nwave, ff0, ff1);
+        first_pair(wp + 3 * nwave, ff0, ff1);
+        parse();
+      } else {
+        packet(nx, wp + nwave, ff0, ff1);
+        first_pair(wp + 2 * nwave, ff0, ff1);
+      }
       yu::iov_walk_reset(W);
       vi = 0;
     }
@@ -2393,7 +2506,27 @@ __global__ __launch_bounds__(256) void k_iov(const yu_iovec *views_, const uint6
     }
     if (!fc.last) return true;
     uint32_t sA = group_total<64>(accA), sB = group_total<64>(accB);
-    if (lead) {
+    if constexpr (DG) {
+      if (lead) {
+        const uint32_t len = fc.len & 0x7FFFFFFFu;
+        const yu::IovDg d = {0u, 0u, fc.f, fc.tl, fc.meta};
+        uint32_t r0, r1;
+        bool st0, st1;
+        yu::iov_dg_value(d, mode, len, fc.hs, fc.ps, sA - jA, sB - jB, r0, r1, st0, st1);
+        if (A.out) {
+          if (mode == YU_MODE_TX_DATAGRAM) {
+            A.out[2 * p] = (uint16_t)r0;
+            A.out[2 * p + 1] = (uint16_t)r1;
+          } else {
+            A.out[p] = (uint16_t)r0;
+          }
+        }
+        if (FILL && !(fc.len >> 31)) {  // binary.BigEndian.PutUint16 through the views
+          if (st0) put_be16_at((uint8_t *)(uintptr_t)fc.ip0, (uint8_t *)(uintptr_t)fc.ip1, r0);
+          if (st1) put_be16_at((uint8_t *)(uintptr_t)fc.fp0, (uint8_t *)(uintptr_t)fc.fp1, r1);
+        }
+      }
+    } else if (lead) {
       const uint32_t len = fc.len & 0x7FFFFFFFu;
       const bool fld = tx && len >= f + 2u;  // the whole field lies in the packet
       if (fld) {
@@ -2594,6 +2727,8 @@ typedef void (*IovFn)(const yu_iovec *, const uint64_t *, const uint16_t *, cons
 const IovFn kIovFns[yu::kIovKernelCount][3] = {
     {k_iov<4, 0, false>, k_iov<4, 1, false>, k_iov<4, 2, false>},
     {k_iov<4, 0, true>, k_iov<4, 1, true>, k_iov<4, 2, true>},
+    {k_iov<4, 0, false, true>, k_iov<4, 1, false, true>, k_iov<4, 2, false, true>},
+    {k_iov<4, 0, true, true>, k_iov<4, 1, true, true>, k_iov<4, 2, true, true>},
 };
 
 // The scatter-gather device calls. The tables are device memory and are not
@@ -2622,6 +2757,32 @@ int batch_iov(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int 
   a.mode = mode;
   hipLaunchKernelGGL(kIovFns[p.kernel][p.policy], dim3(p.blocks), dim3(256), 0, (hipStream_t)stream,
                      views, first_iov, initial_arr, addrs, a);
+  return hip_status(hipGetLastError());
+}
+
+// The same for whole IPv4 datagrams: the modes that parse headers out of the
+// packet, which take no side arrays.
+int batch_iov_datagram(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode,
+                       uint16_t *out, bool fill, void *stream) {
+  if (mode < 0 || mode >= YU_MODE_COUNT) return YU_EINVAL;      // EINVAL:mode
+  if (!yu::iov_dg_mode_ok(mode)) return YU_EINVAL;               // EINVAL:mode (a whole-packet sum: yu_csum_batch_iov takes it)
+  if (fill && !yu::iov_dg_mode_tx(mode)) return YU_EINVAL;       // EINVAL:fill-mode (VERIFY_IPV4, VERIFY_RX store no field)
+  if (!out && !fill && n) return YU_EINVAL;                      // EINVAL:out
+  if (out && !aligned(out, 2)) return YU_EINVAL;                 // EINVAL:side-align
+  if (n == 0) return YU_OK;
+  if (!first_iov || !aligned(first_iov, 8) || !aligned(views, 8)) return YU_EINVAL;  // EINVAL:offsets
+  if (!views) return YU_EINVAL;                                                     // EINVAL:data
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return hip_status(e);
+  const yu::IovPlan p = yu::plan_iov(n, mode, fill, cu_count(dev), yu::env_knobs());
+  IovArgs a;
+  a.out = out;
+  a.n = n;
+  a.initial = 0;
+  a.mode = mode;
+  hipLaunchKernelGGL(kIovFns[p.kernel][p.policy], dim3(p.blocks), dim3(256), 0, (hipStream_t)stream,
+                     views, first_iov, (const uint16_t *)nullptr, (const uint8_t *)nullptr, a);
   return hip_status(hipGetLastError());
 }
 
@@ -2694,6 +2855,22 @@ int yu_csum_fill_iov(const yu_iovec *views, const uint64_t *first_iov, uint64_t 
 const char *yu_iov_variant_n(int mode, uint64_t n, int fill) {
   if (mode < 0 || mode >= YU_MODE_COUNT || !yu::iov_mode_ok(mode)) return "";
   if (fill && !yu::iov_mode_tx(mode)) return "";
+  return yu::plan_iov(n, mode, fill != 0, 256, yu::env_knobs()).name;
+}
+
+int yu_csum_batch_iov_datagram(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode,
+                               uint16_t *out, void *stream) {
+  return batch_iov_datagram(views, first_iov, n, mode, out, false, stream);
+}
+
+int yu_csum_fill_iov_datagram(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode,
+                              uint16_t *out, void *stream) {
+  return batch_iov_datagram(views, first_iov, n, mode, out, true, stream);
+}
+
+const char *yu_iov_datagram_variant_n(int mode, uint64_t n, int fill) {
+  if (mode < 0 || mode >= YU_MODE_COUNT || !yu::iov_dg_mode_ok(mode)) return "";
+  if (fill && !yu::iov_dg_mode_tx(mode)) return "";
   return yu::plan_iov(n, mode, fill != 0, 256, yu::env_knobs()).name;
 }
 

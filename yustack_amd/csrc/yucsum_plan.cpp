@@ -284,13 +284,20 @@ Plan plan(const Shape &s, int cus, const Knobs &k) {
 
 // k_iov: a wave per packet on the over-subscribed grid of the other
 // wave-per-packet kernels (64 blocks per CU, YU_BLOCKS_PER_CU overrides); the
-// load policy is YU_NT's, else slot 2. `mode` does not enter yet: every mode the
-// form takes is a whole-packet sum on the same kernel.
+// load policy is YU_NT's, else slot 2. `mode` picks the kind: the whole-packet
+// sums share one kernel, the modes that parse an IPv4 header out of the packet
+// (IPV4, VERIFY_IPV4, VERIFY_RX, TX_DATAGRAM) the dg one; the grid is the same.
 IovPlan plan_iov(uint64_t n, int mode, bool fill, int cus, const Knobs &k) {
-  (void)mode;
+  const bool dg = mode == YU_MODE_IPV4 || mode == YU_MODE_VERIFY_IPV4 || mode == YU_MODE_VERIFY_RX ||
+                  mode == YU_MODE_TX_DATAGRAM;
   IovPlan p;
-  p.kernel = fill ? k_iov4_fill : k_iov4;
-  p.name = fill ? "k_iov<4,fill>" : "k_iov<4>";
+  if (dg) {
+    p.kernel = fill ? k_iov4_dg_fill : k_iov4_dg;
+    p.name = fill ? "k_iov<4,dg,fill>" : "k_iov<4,dg>";
+  } else {
+    p.kernel = fill ? k_iov4_fill : k_iov4;
+    p.name = fill ? "k_iov<4,fill>" : "k_iov<4>";
+  }
   p.policy = (uint8_t)(k.nt >= 0 ? k.nt : 2);
   const uint64_t cap = (uint64_t)cus * (k.blocks_per_cu ? k.blocks_per_cu : 64u);
   uint64_t blocks = (n + 3) / 4;  // 4 waves per block, a wave per packet

@@ -176,14 +176,15 @@ Plan plan(const Shape &s, int cus, const Knobs &k);
 // The scatter-gather device calls (yu_csum_batch_iov / yu_csum_fill_iov) have a
 // plan of their own: one kernel family, k_iov (yucsum_iov.h), which is not one
 // of YU_KERNELS because no uniform or ragged batch ever takes it.
-enum IovKernel : uint8_t { k_iov4, k_iov4_fill, kIovKernelCount };
+enum IovKernel : uint8_t { k_iov4, k_iov4_fill, k_iov4_dg, k_iov4_dg_fill, kIovKernelCount };
 struct IovPlan {
   IovKernel kernel;
   uint8_t policy;  // load-policy slot: 0 plain, 1 nt, 2 plain for a step's first slot, nt for the rest
   uint32_t blocks;
-  const char *name;  // what yu_iov_variant_n returns
+  const char *name;  // what yu_iov_variant_n / yu_iov_datagram_variant_n return
 };
-// mode: one of the modes the form takes (yu::iov_mode_ok).
+// mode: one of the modes the form takes (yu::iov_mode_ok), or one of the whole-
+// datagram modes of yu_csum_batch_iov_datagram (yu::iov_dg_mode_ok): the dg kernels.
 IovPlan plan_iov(uint64_t n, int mode, bool fill, int cus, const Knobs &k);
 
 }  // namespace yu
