@@ -46,6 +46,7 @@
 #include <vector>
 
 #include "yucsum.h"
+#include "yucsum_hostgeom.h"
 #include "yucsum_internal.h"
 
 namespace {
@@ -57,6 +58,18 @@ constexpr uint64_t kSliceBytes = YU_HOST_SLICE_BYTES;  // 32 MiB
 // packets under 128 bytes reach it; 256K of 64-byte packets is 16 MiB, still
 // hundreds of microseconds of PCIe per slice.
 constexpr uint64_t kSlicePkts = YU_HOST_SLICE_PACKETS;  // 256K
+
+namespace hg = yu::hostgeom;  // the slice, route and shard arithmetic, the field rule
+
+// Where slices are cut: the constants above, or less under the measurement
+// knobs YU_HOST_SLICE_BYTES / YU_HOST_SLICE_PACKETS (YU_TUNING=1 only; a value
+// outside [1, the constant] is ignored). Only the cut moves: the pools' bounds
+// and give_back keep the constants, so a tuned process can only hold less.
+const hg::SliceLimits &slice_limits() {
+  static const hg::SliceLimits v = {hg::slice_knob(yu::tuning_env("YU_HOST_SLICE_BYTES"), kSliceBytes),
+                                    hg::slice_knob(yu::tuning_env("YU_HOST_SLICE_PACKETS"), kSlicePkts)};
+  return v;
+}
 
 int hip_rc(hipError_t e) {
   if (e == hipSuccess) return YU_OK;
@@ -92,10 +105,10 @@ struct Slot {
 // (the allocations of Ctx::reserve: packet bytes, addrs 8, initial 2, results 4,
 // offsets 8, coherent results 4 per packet, one more offset, the 64-byte flag)
 constexpr uint64_t pinned_bytes(uint64_t data_bytes, uint64_t pk, int slots = kSlots) {
-  return slots * ((data_bytes ? data_bytes : 16) + pk * 8 + pk * 2 + pk * 4 + (pk + 1) * 8 + pk * 4 + 64);
+  return slots * ((data_bytes < 16 ? 16 : data_bytes) + pk * 8 + pk * 2 + pk * 4 + (pk + 1) * 8 + pk * 4 + 64);
 }
 constexpr uint64_t device_bytes(uint64_t data_bytes, uint64_t pk, int slots = kSlots) {
-  return slots * ((data_bytes ? data_bytes : 16) + pk * 8 + pk * 2 + pk * 4 + (pk + 1) * 8);
+  return slots * ((data_bytes < 16 ? 16 : data_bytes) + pk * 8 + pk * 2 + pk * 4 + (pk + 1) * 8);
 }
 // The default direct cut-over (bytes of one burst that the kernel reads from
 // host memory itself; see `direct` below).
@@ -191,7 +204,7 @@ struct Ctx {
       Slot &x = s[k];
       YU_TRY(hipStreamCreateWithFlags(&x.st, hipStreamNonBlocking));
       YU_TRY(hipEventCreateWithFlags(&x.done, hipEventDisableTiming));
-      YU_TRY_ALLOC(hipHostMalloc((void **)&x.h_data, data_bytes ? data_bytes : 16, 0));
+      YU_TRY_ALLOC(hipHostMalloc((void **)&x.h_data, data_bytes < 16 ? 16 : data_bytes, 0));
       YU_TRY_ALLOC(hipHostMalloc((void **)&x.h_addrs, pk * 8, 0));
       YU_TRY_ALLOC(hipHostMalloc((void **)&x.h_init, pk * 2, 0));
       // results: up to 2 per packet (YU_MODE_OUTPUTS)
@@ -200,7 +213,7 @@ struct Ctx {
       YU_TRY_ALLOC(hipHostMalloc((void **)&x.h_outc, pk * 4, hipHostMallocCoherent));
       YU_TRY_ALLOC(hipHostMalloc((void **)&x.h_flag, 64, hipHostMallocCoherent));
       *x.h_flag = 0;
-      YU_TRY_ALLOC(hipMalloc((void **)&x.d_data, data_bytes ? data_bytes : 16));
+      YU_TRY_ALLOC(hipMalloc((void **)&x.d_data, data_bytes < 16 ? 16 : data_bytes));
       YU_TRY_ALLOC(hipMalloc((void **)&x.d_addrs, pk * 8));
       YU_TRY_ALLOC(hipMalloc((void **)&x.d_init, pk * 2));
       YU_TRY_ALLOC(hipMalloc((void **)&x.d_out, pk * 4));
@@ -547,7 +560,7 @@ int pipeline(int device, const Layout &L, uint64_t n, const uint16_t *h_init,
     if (cnt > max_pk) max_pk = cnt;
     first += cnt;
   }
-  const bool burst = max_pk == n && max_b <= direct_max();
+  const bool burst = hg::is_burst(max_pk, n, max_b, direct_max());
   Lease lease(device, burst ? kBurst : kBulk);
   Ctx &c = lease.ctx();
   int rc = c.reserve(max_b, max_pk);
@@ -628,8 +641,8 @@ struct UniformLayout {
   uint16_t initial;
   bool pin_in;
   bool ragged() const { return false; }
-  uint64_t count(uint64_t first) const { return n - first < slice ? n - first : slice; }
-  uint64_t bytes(uint64_t, uint64_t cnt) const { return (cnt - 1) * stride + len; }
+  uint64_t count(uint64_t first) const { return hg::uniform_count(n, slice, first); }
+  uint64_t bytes(uint64_t, uint64_t cnt) const { return hg::uniform_bytes(stride, len, cnt); }
   const uint8_t *stage(Slot &x, uint64_t first, uint64_t cnt) const {
     const uint8_t *src = h_data + first * stride;
     const uint64_t b = bytes(first, cnt);
@@ -643,20 +656,6 @@ struct UniformLayout {
   }
 };
 
-// Slices of whole packets, each up to kSliceBytes (a longer packet is a
-// slice of its own); `span(i)` = bytes of packet i.
-template <class Span>
-uint64_t byte_slice(uint64_t first, uint64_t n, const Span &span) {
-  uint64_t cnt = 0, b = 0;
-  while (first + cnt < n && cnt < kSlicePkts) {
-    const uint64_t l = span(first + cnt);
-    if (cnt && b + l > kSliceBytes) break;
-    b += l;
-    ++cnt;
-  }
-  return cnt;
-}
-
 // packet i = data[off[i], off[i+1]) (tun burst, back to back)
 struct RaggedLayout {
   const uint8_t *h_data;
@@ -666,10 +665,10 @@ struct RaggedLayout {
   uint16_t initial;
   bool pin_in;
   bool ragged() const { return true; }
-  uint64_t count(uint64_t first) const {
-    return byte_slice(first, n, [&](uint64_t i) { return off[i + 1] - off[i]; });
-  }
-  uint64_t bytes(uint64_t first, uint64_t cnt) const { return off[first + cnt] - off[first]; }
+  // (slices of whole packets, each up to the byte limit; a longer packet is a
+  // slice of its own: hg::byte_slice)
+  uint64_t count(uint64_t first) const { return hg::ragged_count(off, n, first, slice_limits()); }
+  uint64_t bytes(uint64_t first, uint64_t cnt) const { return hg::ragged_bytes(off, first, cnt); }
   const uint8_t *stage(Slot &x, uint64_t first, uint64_t cnt) const {
     const uint64_t o0 = off[first];
     for (uint64_t i = 0; i <= cnt; ++i) x.h_off[i] = off[first + i] - o0;
@@ -694,19 +693,9 @@ struct IovLayout {
   int mode;
   uint16_t initial;
   bool ragged() const { return true; }
-  uint64_t plen(uint64_t i) const {
-    uint64_t l = 0;
-    for (uint64_t v = first_iov[i]; v < first_iov[i + 1]; ++v) l += iov[v].len;
-    return l;
-  }
-  uint64_t count(uint64_t first) const {
-    return byte_slice(first, n, [&](uint64_t i) { return plen(i); });
-  }
-  uint64_t bytes(uint64_t first, uint64_t cnt) const {
-    uint64_t b = 0;
-    for (uint64_t i = first; i < first + cnt; ++i) b += plen(i);
-    return b;
-  }
+  uint64_t plen(uint64_t i) const { return hg::iov_plen(iov, first_iov, i); }
+  uint64_t count(uint64_t first) const { return hg::iov_count(iov, first_iov, n, first, slice_limits()); }
+  uint64_t bytes(uint64_t first, uint64_t cnt) const { return hg::iov_bytes(iov, first_iov, first, cnt); }
   const uint8_t *stage(Slot &x, uint64_t first, uint64_t cnt) const {
     uint64_t o = 0;
     for (uint64_t i = 0; i < cnt; ++i) {
@@ -873,28 +862,10 @@ int fan_out(const int *devices, int ndev, const std::vector<uint64_t> &bounds,
   return rc;
 }
 
-// Even packet counts (uniform, iovec).
-std::vector<uint64_t> even_bounds(uint64_t n, int ndev) {
-  std::vector<uint64_t> b(ndev + 1);
-  for (int i = 0; i <= ndev; ++i) b[i] = (uint64_t)((unsigned __int128)n * i / ndev);
-  return b;
-}
-
-// Packet boundaries closest below an even split of the bytes (ragged), as
-// yustack_amd/shard.py does for the device-resident bench.
-std::vector<uint64_t> byte_bounds(const uint64_t *off, uint64_t n, int ndev) {
-  std::vector<uint64_t> b(ndev + 1);
-  const uint64_t o0 = off[0], tot = off[n] - off[0];
-  b[0] = 0;
-  b[ndev] = n;
-  for (int i = 1; i < ndev; ++i) {
-    const uint64_t target = o0 + (uint64_t)((unsigned __int128)tot * i / ndev);
-    uint64_t k = (uint64_t)(std::lower_bound(off, off + n + 1, target) - off);
-    if (k > n) k = n;
-    b[i] = std::max(k, b[i - 1]);
-  }
-  return b;
-}
+// The shard bounds (even packet counts: uniform, iovec; packet boundaries closest
+// below an even split of the bytes: ragged) are yucsum_hostgeom.h's.
+using hg::byte_bounds;
+using hg::even_bounds;
 
 }  // namespace
 
@@ -913,11 +884,7 @@ extern "C" int yu_csum_batch_host_uniform(const uint8_t *h_data,
   if (len > YU_MAX_RAW_LEN) return YU_EINVAL;                                // EINVAL:len-raw
   if (span_wraps(h_data, stride, len, n)) return YU_EINVAL;                  // EINVAL:span
   return on_device(device, [&] {
-    const uint64_t pstride = stride ? stride : 1;
-    uint64_t slice = kSliceBytes / pstride;
-    if (slice > kSlicePkts) slice = kSlicePkts;
-    if (slice < 1) slice = 1;
-    if (slice > n) slice = n;
+    const uint64_t slice = hg::uniform_slice(stride, n, slice_limits());
     UniformLayout L{h_data, stride, n, slice, len, mode, initial, is_pinned(h_data)};
     return pipeline(device, L, n, h_initial_arr, h_addrs, h_out);
   });
@@ -1072,52 +1039,14 @@ extern "C" int yu_host_staging_trim(int device) {
 // ---------------------------------------------------------------------
 namespace {
 
-using yu::l4_field;  // the kernels' protocol tables (yucsum_internal.h)
-using yu::l4_min;
-using yu::mode_field;
-
 bool tx_mode(int m) { return yu::mode_fills(m); }
 
-// Byte k of packet i, through a layout's accessor (nullptr past the packet).
-// set(i) writes packet i's field; the packets are split over the copy pool.
-template <class At>
-void put_field(const At &at, uint64_t i, uint32_t f, uint16_t v) {
-  uint8_t *hi = at(i, f), *lo = at(i, f + 1);
-  if (!hi || !lo) return;
-  *hi = (uint8_t)(v >> 8);
-  *lo = (uint8_t)v;
-}
-
-// TX_DATAGRAM: both fields of datagram i where the device defined them
-// (include/yucsum.h): the contract 20 <= HeaderLength() <= TotalLength() <=
-// len read from the bytes, the transport field when the protocol has one and
-// the segment holds its header — the rule the kernels apply.
-template <class At>
-void put_datagram_fields(const At &at, uint64_t i, const uint16_t *res) {
-  const uint8_t *b0 = at(i, 0), *b2 = at(i, 2), *b3 = at(i, 3), *b9 = at(i, 9);
-  if (!at(i, 19)) return;  // shorter than 20 bytes
-  const uint32_t hl = (uint32_t)(*b0 & 0xFu) * 4u, tl = (uint32_t)*b2 << 8 | *b3;
-  if (hl < 20u || hl > tl || !at(i, tl - 1u)) return;
-  put_field(at, i, 10, res[2 * i]);
-  const uint32_t proto = *b9;
-  const uint32_t fo = l4_field(proto);
-  if (fo && tl - hl >= l4_min(proto)) put_field(at, i, hl + fo, res[2 * i + 1]);
-}
-
+// The per-packet rule (put_field, put_datagram_fields, put_packet_fields) and the
+// layouts' accessors are yucsum_hostgeom.h's; at(i, k) is byte k of packet i
+// (nullptr past the packet). The packets are split over the copy pool.
 template <class At>
 void set_fields(uint64_t n, int mode, const uint16_t *res, const At &at) {
-  const uint32_t f = mode_field(mode);
-  auto one = [&](uint64_t i) {
-    if (mode == YU_MODE_TX_DATAGRAM) {
-      put_datagram_fields(at, i, res);
-      return;
-    }
-    if (mode == YU_MODE_IPV4) {  // the field must lie inside the header
-      const uint8_t *b0 = at(i, 0);
-      if (!b0 || (uint32_t)(*b0 & 0xFu) * 4u < f + 2u) return;
-    }
-    put_field(at, i, f, res[i]);
-  };
+  auto one = [&](uint64_t i) { hg::put_packet_fields(mode, i, res, at); };
   constexpr uint64_t kParMin = 1u << 16;
   CopyPool &pool = CopyPool::get();
   const uint64_t parts = std::min<uint64_t>((uint64_t)pool.threads() + 1, n / kParMin);
@@ -1158,9 +1087,7 @@ extern "C" int yu_csum_fill_host_uniform(uint8_t *h_data, uint64_t stride, uint3
   int rc = yu_csum_batch_host_uniform(h_data, stride, len, n, mode, h_initial_arr, initial,
                                       h_addrs, r.p, device);
   if (rc) return rc;
-  set_fields(n, mode, r.p, [&](uint64_t i, uint32_t k) -> uint8_t * {
-    return k < len ? h_data + i * stride + k : nullptr;
-  });
+  set_fields(n, mode, r.p, hg::UniformAt{h_data, stride, len});
   return YU_OK;
 }
 
@@ -1175,9 +1102,7 @@ extern "C" int yu_csum_fill_host_ragged(uint8_t *h_data, const uint64_t *h_offse
   int rc = yu_csum_batch_host_ragged(h_data, h_offsets, n, mode, h_initial_arr, initial, h_addrs,
                                      r.p, device);
   if (rc) return rc;
-  set_fields(n, mode, r.p, [&](uint64_t i, uint32_t k) -> uint8_t * {
-    return k < h_offsets[i + 1] - h_offsets[i] ? h_data + h_offsets[i] + k : nullptr;
-  });
+  set_fields(n, mode, r.p, hg::RaggedAt{h_data, h_offsets});
   return YU_OK;
 }
 
@@ -1191,14 +1116,6 @@ extern "C" int yu_csum_fill_host_iov(const yu_iovec *iov, const uint64_t *first_
   int rc = yu_csum_batch_host_iov(iov, first_iov, n, mode, h_initial_arr, initial, h_addrs, r.p,
                                   device);
   if (rc) return rc;
-  // byte k of packet i: walk its views (the field may straddle two of them)
-  set_fields(n, mode, r.p, [&](uint64_t i, uint32_t k) -> uint8_t * {
-    uint64_t at = k;
-    for (uint64_t v = first_iov[i]; v < first_iov[i + 1]; ++v) {
-      if (at < iov[v].len) return (uint8_t *)iov[v].base + at;
-      at -= iov[v].len;
-    }
-    return nullptr;
-  });
+  set_fields(n, mode, r.p, hg::IovAt{iov, first_iov});
   return YU_OK;
 }
