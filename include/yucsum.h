@@ -67,7 +67,8 @@ extern "C" {
 /* YU_EINVAL has read no packet byte and written nothing.               */
 /*                                                                      */
 /*  [mode]          mode is not 0 .. YU_MODE_COUNT-1 (every call); the   */
-/*                  scatter-gather device calls (yu_csum_*_iov): also   */
+/*                  scatter-gather device calls (yu_csum_*_iov, the      */
+/*                  packing yu_csum_pack_*_iov included): also           */
 /*                  IPV4, VERIFY_IPV4, VERIFY_RX and TX_DATAGRAM, which  */
 /*                  parse headers out of the packet; the whole-datagram  */
 /*                  calls (yu_csum_*_iov_datagram) take those four and   */
@@ -78,14 +79,16 @@ extern "C" {
 /*                  batch, n == 0, is a no-op returning YU_OK).          */
 /*  [fill-mode]     a fill call (yu_csum_fill_*) with a mode that has no */
 /*                  field to write: RAW, VERIFY_* (or no mode at all);   */
-/*                  yu_csum_fill_iov: any mode but UDP, TCP and ICMP;    */
+/*                  yu_csum_fill_iov and yu_csum_pack_fill_iov: any mode */
+/*                  but UDP, TCP and ICMP;                               */
 /*                  yu_csum_fill_iov_datagram: VERIFY_IPV4, VERIFY_RX.   */
 /*  [side-align]    device calls: initial_arr not 2-byte aligned, addrs  */
 /*                  not 4-byte aligned, out not 2-byte aligned.          */
 /*  [data]          data == NULL with n > 0 (device calls), h_data ==    */
 /*                  NULL while the packets hold bytes (host calls), iov  */
 /*                  == NULL while first_iov names views; views == NULL  */
-/*                  with n > 0 (yu_csum_*_iov).                          */
+/*                  with n > 0 (yu_csum_*_iov); dst == NULL with n > 0   */
+/*                  (yu_csum_pack_*_iov).                                */
 /*  [len-transport] a packet of a mode other than RAW longer than        */
 /*                  YU_MAX_TRANSPORT_LEN (uniform len; every host ragged */
 /*                  or iov packet). Device ragged batches are not read   */
@@ -98,8 +101,10 @@ extern "C" {
 /*  [offsets]       offsets == NULL, or (device) not 8-byte aligned, or  */
 /*                  (host) decreasing; first_iov == NULL or decreasing;  */
 /*                  yu_csum_*_iov (device tables): first_iov == NULL or  */
-/*                  not 8-byte aligned, views not 8-byte aligned.        */
-/*  [iov-view]      a view with base == NULL and len > 0.                */
+/*                  not 8-byte aligned, views not 8-byte aligned;        */
+/*                  yu_csum_pack_*_iov: also dst_offsets == NULL or not  */
+/*                  8-byte aligned.                                      */
+/*  [iov-view]     a view with base == NULL and len > 0.                */
 /*  [fill-align]    yu_csum_fill_uniform: data or stride not a multiple  */
 /*                  of 4. The uniform writers store whole dwords of each */
 /*                  packet's window, so no dword may hold bytes of two   */
@@ -475,6 +480,65 @@ int yu_csum_batch_iov_datagram(const yu_iovec *views, const uint64_t *first_iov,
 int yu_csum_fill_iov_datagram(const yu_iovec *views, const uint64_t *first_iov,
                               uint64_t n, int mode, uint16_t *out, void *stream);
 
+/* Scatter-gather device batches summed and packed in one pass (Linux's
+ * csum_and_copy over a view list): the reference concatenates a received
+ * VectorisedView with ToView() (buffer/view.go:93-102) before it hands the
+ * bytes up, and writev gathers header and payload into one wire image
+ * (link/tundev/tundev.go:171-196). These calls do what yu_csum_batch_iov does,
+ * on its layout and call discipline (device CSR tables and bases, asynchronous
+ * on `stream`, no allocation, no synchronisation, graph-capturable, YU_ENODEV
+ * without a device, n == 0 a no-op returning YU_OK after the checks that do not
+ * need n), and also store each packet's bytes in one piece: one read of the
+ * views, one write of the copy.
+ *
+ * Copy: the bytes of packet i, the concatenation of its views, len_i of them,
+ * are stored at dst[dst_offsets[i], dst_offsets[i] + len_i). `dst_offsets` holds
+ * n + 1 DEVICE uint64 values, 8-byte aligned, as the `offsets` of the ragged
+ * form; `dst` is a DEVICE pointer of any alignment. A packet may have slack,
+ * len_i < dst_offsets[i+1] - dst_offsets[i]; slack bytes are never written.
+ * When no packet has slack, (dst, dst_offsets) is exactly the ragged batch
+ * yu_csum_batch_ragged takes. dst[0, dst_offsets[n]) must not overlap a byte of
+ * any view named, the tables, the side arrays or `out`; this is not checked.
+ *
+ * Value: out[i] is exactly what yu_csum_batch_iov returns with the same side
+ * arguments. Modes: RAW, UDP, TCP, ICMP, VERIFY_TCP, VERIFY_UDP; the TX modes
+ * take the field as 0 wherever its two bytes lie.
+ *
+ * Field bytes in the copy: yu_csum_pack_iov copies them as they are.
+ * yu_csum_pack_fill_iov (UDP, TCP, ICMP; `out` may be NULL) gives them the
+ * value, big-endian, iff len_i >= f + 2 and the packet is in contract. Neither
+ * call ever writes a source view, so views may be shared between packets in
+ * both: a header template named by many packets gets its own field in each
+ * copy, which yu_csum_fill_iov has to forbid. Every byte of dst is stored by
+ * one store of the call, the field bytes included: they are held back until
+ * the value is known.
+ *
+ * Out of contract: a packet with len_i > dst_offsets[i+1] - dst_offsets[i], at
+ * which dst_offsets decreases, or out of yu_csum_batch_iov's contract (more
+ * than YU_MAX_TRANSPORT_LEN bytes, first_iov decreasing). It gets an
+ * unspecified value and unspecified bytes inside its own span
+ * [dst_offsets[i], min(dst_offsets[i+1], dst_offsets[n])) (empty if that is no
+ * range) and no field value; never a fault or a hang. No call writes a byte of
+ * dst outside dst[0, dst_offsets[n]) or outside a packet's own span: each view's
+ * copy is cut to the room left. Every other packet is exact in value and
+ * bytes. Reads are those of yu_csum_batch_iov: only dwords that hold bytes of
+ * the views named.
+ *
+ * YU_EINVAL (Preconditions above): [mode], [fill-mode], [out], [side-align] as
+ * for yu_csum_batch_iov; [offsets]: also dst_offsets == NULL or not 8-byte
+ * aligned; [data]: views == NULL or dst == NULL with n > 0.
+ *
+ * IPV4, VERIFY_IPV4, VERIFY_RX and TX_DATAGRAM are not taken yet: run
+ * yu_csum_fill_ragged(TX_DATAGRAM) on the packed copy. */
+int yu_csum_pack_iov(const yu_iovec *views, const uint64_t *first_iov,
+                     uint64_t n, int mode, const uint16_t *initial_arr,
+                     uint16_t initial, const uint8_t *addrs, uint8_t *dst,
+                     const uint64_t *dst_offsets, uint16_t *out, void *stream);
+int yu_csum_pack_fill_iov(const yu_iovec *views, const uint64_t *first_iov,
+                          uint64_t n, int mode, const uint16_t *initial_arr,
+                          uint16_t initial, const uint8_t *addrs, uint8_t *dst,
+                          const uint64_t *dst_offsets, uint16_t *out, void *stream);
+
 /* Host-memory field writer: the matching yu_csum_batch_host_* call (TX modes
  * UDP/TCP/IPV4/ICMP/TX_DATAGRAM only), then each result stored big-endian into the
  * packet's checksum field in host memory, as the device writer does
@@ -608,6 +672,8 @@ const char *yu_ragged_fill_variant_n(int mode, uint64_t n);
 const char *yu_iov_variant_n(int mode, uint64_t n, int fill);
 /* The same for the whole-datagram calls (fill != 0: yu_csum_fill_iov_datagram). */
 const char *yu_iov_datagram_variant_n(int mode, uint64_t n, int fill);
+/* The same for the packing calls (fill != 0: yu_csum_pack_fill_iov). */
+const char *yu_iov_pack_variant_n(int mode, uint64_t n, int fill);
 
 #ifdef __cplusplus
 }

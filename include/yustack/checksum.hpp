@@ -280,6 +280,28 @@ inline void FillIov(const yu_iovec *views, const uint64_t *first_iov, uint64_t n
   if (rc) throw Error(rc, "yu_csum_fill_iov");
 }
 
+// The same sums and, in the same pass, the packets in one piece: packet i's
+// bytes are stored at dst[dst_offsets[i] ...] (VectorisedView.ToView() +
+// Checksum, buffer/view.go:93-102; n + 1 DEVICE offsets, slack allowed, never
+// written). With tight offsets (dst, dst_offsets) is the batch Ragged takes.
+// PackFillIov (UDP, TCP, ICMP) stores each value into the field of the copy; the
+// views are never written, so they may be shared between packets.
+inline void PackIov(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, Mode m,
+                    uint8_t *dst, const uint64_t *dst_offsets, uint16_t *out, const Side &s = {},
+                    void *stream = nullptr) {
+  int rc = yu_csum_pack_iov(views, first_iov, n, m, s.initial_arr, s.initial, s.addrs, dst,
+                            dst_offsets, out, stream);
+  if (rc) throw Error(rc, "yu_csum_pack_iov");
+}
+
+inline void PackFillIov(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, Mode m,
+                        uint8_t *dst, const uint64_t *dst_offsets, uint16_t *out = nullptr,
+                        const Side &s = {}, void *stream = nullptr) {
+  int rc = yu_csum_pack_fill_iov(views, first_iov, n, m, s.initial_arr, s.initial, s.addrs, dst,
+                                 dst_offsets, out, stream);
+  if (rc) throw Error(rc, "yu_csum_pack_fill_iov");
+}
+
 // Host buffers in, host results out (pinned staging + pipelined copies, or
 // the direct path for bursts up to 4 MiB). Here `Side` holds HOST pointers.
 // A device list shards the batch over several GPUs (the *_multi calls).

@@ -3,7 +3,7 @@
 
 Workload: n packets, each a header view (hdr bytes, in a header pool with a 64-byte
 pitch) and a payload view (pay bytes, in a payload pool), TCP or UDP with `addrs`.
-Three alternatives, alternated launch by launch within one process, each timed with
+The alternatives, alternated launch by launch within one process, each timed with
 HIP events, medians over --launches launches:
 
   iov         yu_csum_batch_iov on a prebuilt device table (the call a C user makes)
@@ -12,6 +12,9 @@ HIP events, medians over --launches launches:
               header slice and the payload), then checksum_uniform: what the caller
               had to do before
   packed      checksum_uniform on bytes already packed: the floor
+  pack_fused  yu_csum_pack_iov on the same table into a preallocated dst and offsets:
+              the sums and the packed copy in one launch (what pack+sum delivers in
+              two); its dst and values are checked against the oracle before timing
 
 Whole-datagram workloads (yu_csum_batch_iov_datagram / yu_csum_fill_iov_datagram): n
 1500-byte TCP datagrams, each a 40-byte header view (IPv4 + TCP header) and a 1460-byte
@@ -70,6 +73,8 @@ def run(name, n, launches, sets, dev):
     L, m = _lib.lib(), batch.MODES[mode]
     stream = torch.cuda.current_stream(dev).cuda_stream
     ln = hl + pl
+    dst = torch.zeros(n * ln, dtype=torch.uint8, device=dev)
+    dst_offsets = torch.arange(n + 1, device=dev) * ln
 
     def iov(k):
         _lib.check(L.yu_csum_batch_iov(tables[k].data_ptr(), first.data_ptr(), n, m, None, 0, addrs.data_ptr(),
@@ -86,16 +91,23 @@ def run(name, n, launches, sets, dev):
     def floor(k):
         batch.checksum_uniform(packed[k].view(-1), ln, ln, n, mode, addrs=addrs, out=out)
 
-    alts = {"iov": iov, "iov_py": iov_py, "pack+sum": pack_sum, "packed": floor}
+    def pack_fused(k):
+        _lib.check(L.yu_csum_pack_iov(tables[k].data_ptr(), first.data_ptr(), n, m, None, 0, addrs.data_ptr(),
+                                      dst.data_ptr(), dst_offsets.data_ptr(), out.data_ptr(), stream),
+                   "yu_csum_pack_iov")
+
+    alts = {"iov": iov, "iov_py": iov_py, "pack+sum": pack_sum, "packed": floor, "pack_fused": pack_fused}
     # every alternative computes the same values, and they are the oracle's
     want = None
     for a, fn in alts.items():
+        out.zero_()
         fn(0)
         got = out.cpu().numpy().copy()
         if want is None:
             want = O.C().batch(packed[0].cpu().numpy().reshape(-1), m, stride=ln, length=ln, n=n,
                                addrs=addrs.cpu().numpy(), threads=16)
         assert np.array_equal(got, want), a
+    assert torch.equal(dst, packed[0].view(-1)), "pack_fused: dst is not the packed bytes"
     times = {a: [] for a in alts}
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in alts]
     for it in range(launches + 3):
@@ -117,9 +129,14 @@ def run(name, n, launches, sets, dev):
         "us_min": {a: round(min(t), 2) for a, t in times.items()},
         "iov_vs_pack_sum": round(med["iov"] / med["pack+sum"], 3),
         "iov_vs_floor": round(med["iov"] / med["packed"], 3),
+        "pack_variant": batch.iov_pack_variant(mode, n),
+        "pack_fused_vs_pack_sum": round(med["pack_fused"] / med["pack+sum"], 3),
+        "pack_fused_vs_floor": round(med["pack_fused"] / med["packed"], 3),
         "iov_algorithmic_bytes": alg,
         "iov_fraction_of_hbm_peak": round(alg / (med["iov"] * 1e-6) / PEAK, 3),
         "floor_fraction_of_hbm_peak": round(n * (ln + 8 + 2) / (med["packed"] * 1e-6) / PEAK, 3),
+        # one read of the views and tables, one write of the copy
+        "pack_fused_fraction_of_hbm_peak": round((alg + n * (ln + 16)) / (med["pack_fused"] * 1e-6) / PEAK, 3),
     }
     print(json.dumps(res), flush=True)
     return res

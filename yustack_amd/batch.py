@@ -2,7 +2,7 @@
 
 Thin Python front end over the C ABI's batched entry points
 (``yu_csum_batch_uniform`` / ``yu_csum_batch_ragged`` / ``yu_csum_batch_iov`` /
-``yu_csum_batch_iov_datagram`` / ``yu_csum_fill_*`` / ``yu_csum_batch_host_uniform``,
+``yu_csum_batch_iov_datagram`` / ``yu_csum_pack_iov`` / ``yu_csum_fill_*`` / ``yu_csum_batch_host_uniform``,
 include/yucsum.h). PyTorch is used only for device
 memory and streams: the arithmetic happens in the hand-written gfx950 kernels of
 ``csrc/yucsum_kernels.hip``. There is no CPU fallback — without a HIP device every
@@ -301,6 +301,98 @@ def checksum_iov_datagrams(pools, view_pool: torch.Tensor, view_off: torch.Tenso
               lambda f, s: f(table.data_ptr(), fi.data_ptr(), n, m, out.data_ptr() if n else None, s))
     out.iov_table = (table, fi)
     return out
+
+
+def _overlaps(a: torch.Tensor, b: torch.Tensor) -> bool:
+    """The address ranges of two contiguous tensors share a byte."""
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    a1, b1 = a0 + a.numel() * a.element_size(), b0 + b.numel() * b.element_size()
+    return a0 < b1 and b0 < a1
+
+
+def pack_iov(pools, view_pool: torch.Tensor, view_off: torch.Tensor, view_len: torch.Tensor,
+             first: torch.Tensor, mode="raw", *, initial: int = 0,
+             initial_arr: torch.Tensor | None = None, addrs: torch.Tensor | None = None,
+             dst: torch.Tensor | None = None, dst_offsets: torch.Tensor | None = None,
+             out: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None,
+             fill: bool = False, validate: bool = True):
+    """Scatter-gather device packets summed and packed into one buffer in one pass
+    (yu_csum_pack_iov / yu_csum_pack_fill_iov): the layout, the table, the modes,
+    the side arguments, ``stream`` and ``out.iov_table`` are :func:`checksum_iov`'s.
+    Returns ``(out, dst, dst_offsets)``: packet i's bytes, the concatenation of its
+    views, lie at ``dst[dst_offsets[i] : dst_offsets[i] + len_i]`` and ``out[i]`` is
+    :func:`checksum_iov`'s value. With tight offsets ``(dst, dst_offsets)`` is the
+    batch :func:`checksum_ragged` takes. ``fill=True`` (UDP, TCP, ICMP) stores each
+    value big-endian into the field of the *copy*; the pools are never written, so
+    views may be shared between packets (one header template for many).
+
+    ``dst_offsets=None``: the tight offsets, an int64 cumsum of the packets' view
+    lengths computed on the device. ``dst=None``: a new tensor of ``dst_offsets[-1]``
+    bytes, which costs one synchronisation to learn that size. Given ``dst`` (a
+    contiguous uint8 CUDA tensor), ``dst_offsets`` (n+1 int64/uint64 entries) and
+    ``validate=False`` the call is capturable in a graph. ``validate`` also checks,
+    on the device, that ``dst_offsets`` is non-decreasing, that every packet has
+    room for its bytes and that ``dst_offsets[-1] <= dst.numel()``, and on the host
+    that ``dst`` meets no pool. Slack bytes between packets are never written."""
+    m = _mode(mode)
+    if m not in IOV_MODES:
+        raise ValueError("pack_iov takes the whole-packet modes: raw, udp, tcp, icmp, verify_tcp, verify_udp")
+    if fill and m not in IOV_FILL_MODES:
+        raise ValueError("fill=True takes udp, tcp or icmp")
+    pools = list(pools)
+    dev, table, fi, n = _iov_table(pools, view_pool, view_off, view_len, first, validate)
+    initial_arr = _opt(initial_arr, torch.uint16, n, dev, "initial_arr")
+    addrs = _opt(addrs, torch.uint8, 8 * n, dev, "addrs")
+    if dst is not None:
+        _dev_u8(dst, "dst")
+        if dst.device != dev:
+            raise TypeError(f"dst must be on {dev}")
+        if any(_overlaps(dst, pool) for pool in pools):
+            raise ValueError("dst overlaps a pool")
+    need_len = dst_offsets is None or (validate and n > 0)
+    if need_len:  # the packets' lengths: sums of their views' lengths
+        nviews = view_len.numel()
+        ends = torch.zeros(nviews + 1, dtype=torch.int64, device=dev)
+        if nviews:
+            ends[1:] = torch.cumsum(table[:, 1].clamp(min=0), 0)
+        f = fi.clamp(0, nviews)
+        plen = (ends[f[1:]] - ends[f[:-1]]).clamp(min=0)
+    if dst_offsets is None:
+        do = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        do[1:] = torch.cumsum(plen, 0)
+    else:
+        do = _dev_index(dst_offsets, "dst_offsets", dev, n + 1)
+        if do.dtype != torch.int64 or do.data_ptr() % 8:
+            raise TypeError("dst_offsets must be 8-byte aligned")
+    if dst is None:
+        dst = torch.empty(max(int(do[-1].item()), 1), dtype=torch.uint8, device=dev)
+    if validate and n > 0:
+        room = do[1:] - do[:-1]
+        ok = torch.stack(((room >= 0).all() & (do[0] >= 0), (room >= plen).all(), do[-1] <= dst.numel())).tolist()
+        if not ok[0]:
+            raise ValueError("dst_offsets is not non-decreasing")
+        if not ok[1]:
+            raise ValueError("a packet has less room in dst than bytes")
+        if not ok[2]:
+            raise ValueError("dst_offsets run past dst")
+    if out is None:
+        out = torch.empty(max(n, 1), dtype=torch.uint16, device=dev)[:n]
+    else:
+        _opt(out, torch.uint16, n, dev, "out")
+    if stream is not None:
+        do.record_stream(stream)
+        dst.record_stream(stream)
+    _iov_call("yu_csum_pack_fill_iov" if fill else "yu_csum_pack_iov", dev, table, fi, stream,
+              lambda f, s: f(table.data_ptr(), fi.data_ptr(), n, m, _ptr(initial_arr), initial & 0xFFFF,
+                             _ptr(addrs), dst.data_ptr(), do.data_ptr(), out.data_ptr() if n else None, s))
+    out.iov_table = (table, fi, do)
+    return out, dst, (do if dst_offsets is None else dst_offsets)
+
+
+def iov_pack_variant(mode="raw", n: int = 1 << 20, fill: bool = False) -> str:
+    """Name of the kernel the packing scatter-gather calls launch ("" for a mode
+    they refuse)."""
+    return lib().yu_iov_pack_variant_n(_mode(mode), n, 1 if fill else 0).decode()
 
 
 def iov_datagram_variant(mode="verify_rx", n: int = 1 << 20, fill: bool = False) -> str:

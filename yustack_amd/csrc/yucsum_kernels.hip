@@ -75,6 +75,10 @@
 //     load slots of 1 KiB of whichever view comes next (yucsum_iov.h). DG: whole IPv4
 //     datagrams (yu_csum_batch_iov_datagram / yu_csum_fill_iov_datagram): the header
 //     gathered into the lanes a packet ahead, the walk windowed to [HL, TL).
+//   k_pack<U, NT, FILL>: the packing scatter-gather calls (yu_csum_pack_iov /
+//     yu_csum_pack_fill_iov, planned by yu::plan_iov_pack): k_iov's walk and sums,
+//     and every byte stored once at its place in one contiguous buffer
+//     (yucsum_iov_pack.h).
 //   All are grid-stride kernels; the grid is sized per CU and over-subscribed
 //   (see blocks_per_cu in yucsum_plan.cpp), except that k_seg narrows it for
 //   small packets (seg_waves).
@@ -89,6 +93,7 @@
 #include "yucsum_dense.h"
 #include "yucsum_internal.h"
 #include "yucsum_iov.h"
+#include "yucsum_iov_pack.h"
 #include "yucsum_plan.h"
 
 namespace {
@@ -2562,6 +2567,310 @@ __global__ __launch_bounds__(256) void k_iov(const yu_iovec *views_, const uint6
 }
 
 // ---------------------------------------------------------------------
+// k_pack<U, NT, FILL>: scatter-gather packets summed and packed in one pass
+// (yu_csum_pack_iov / yu_csum_pack_fill_iov), one wave per packet. The walk, the
+// prefetch of first_iov, records and side data, the slots and the sums are
+// k_iov's whole-packet kind (above; yucsum_iov.h), so the value is k_iov's (a
+// step's loads are summed in the step itself, not one step later). New
+// is the store side (yucsum_iov_pack.h): as a slot is summed, its bytes are
+// shifted to the destination's dword phase (v_alignbyte with the neighbour
+// lane's last dword, one ds_bpermute; across a slot seam the previous slot's last
+// dword, which lane 63 kept) and stored: whole dwords four at a time, the edge
+// dwords of a view's span by 16-bit and byte stores, never a read-modify-write.
+// The field's bytes are held back and stored once by the lead lane when the
+// value is known: the value (FILL, in contract) or the bytes as read. Each
+// packet's dst_offsets pair comes with its records, a packet ahead, as a vector
+// load every lane makes (k_iov leaves no scalar registers for it), so where a
+// packet goes and its room live in vector registers; every view's copy is cut
+// to the room left in the packet's span.
+// ---------------------------------------------------------------------
+struct PackArgs {
+  uint16_t *out;
+  uint8_t *dst;
+  const uint64_t *dst_offsets;
+  uint64_t n;
+  uint32_t initial;
+  int mode;
+};
+
+struct PackPkt {
+  uint64_t g0;
+  uint32_t nv;
+  uint32_t blo, bhi, len;
+  uint32_t sa, sb, si;
+  uint64_t o0, o1;  // every lane: dst_offsets[q], dst_offsets[q + 1] (a vector load: the scalar registers are full)
+};
+
+struct PackFin {
+  bool last;
+  uint32_t len;  // bit 31: out of contract (over kIovLimit, or more bytes than room)
+  uint32_t sa, sb, si;
+};
+
+// The kernel's stores for yucsum_iov_pack.h (global memory; b128 needs 4-byte
+// alignment only).
+struct PackStore {
+  typedef uint32_t __attribute__((ext_vector_type(4), aligned(4))) u32x4a;
+#define YU_GLOBAL_AS __attribute__((address_space(1)))
+  __device__ __forceinline__ void b8(uint64_t a, uint8_t v) const { *(YU_GLOBAL_AS uint8_t *)(uintptr_t)a = v; }
+  __device__ __forceinline__ void b16(uint64_t a, uint16_t v) const { *(YU_GLOBAL_AS uint16_t *)(uintptr_t)a = v; }
+  __device__ __forceinline__ void b32(uint64_t a, uint32_t v) const { *(YU_GLOBAL_AS uint32_t *)(uintptr_t)a = v; }
+  __device__ __forceinline__ void b128(uint64_t a, uint32_t x, uint32_t y, uint32_t z, uint32_t w) const {
+    u32x4a v = {x, y, z, w};
+    *(YU_GLOBAL_AS u32x4a *)(uintptr_t)a = v;
+  }
+#undef YU_GLOBAL_AS
+};
+
+// Keeps a wave-uniform value in vector registers: k_iov's walk fills the scalar
+// ones, and what only addresses a vector load or store needs none.
+template <typename T>
+__device__ __forceinline__ T in_vgpr(T x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+
+template <int U, int NT, bool FILL>
+__global__ __launch_bounds__(256) void k_pack(const yu_iovec *views_, const uint64_t *first_,
+                                              const uint16_t *initial_arr_, const uint8_t *addrs_,
+                                              PackArgs A_) {
+  PackArgs A = A_;
+  A.out = in_vgpr(A_.out);
+  A.dst = in_vgpr(A_.dst);
+  A.dst_offsets = in_vgpr(A_.dst_offsets);
+  const uint16_t *initial_arr = in_vgpr(initial_arr_);
+  const YU_CONST_AS yu_iovec *views = const_as(views_);
+  const YU_CONST_AS uint64_t *first = const_as(first_);
+  const uint32_t lane = threadIdx.x & 63u;
+  const bool lead = lane == 63;
+  const uint64_t wave = grid_wave(0u);
+  const uint64_t nwave = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  const int mode = A.mode;
+  const uint32_t f = yu::iov_mode_field(mode);
+  const bool tx = f != 0;
+  const uint8_t *addrs = in_vgpr(mode_has_pseudo(mode) ? addrs_ : nullptr);
+  const bool have_addrs = mode_has_pseudo(mode) && addrs_ != nullptr, have_initial = initial_arr_ != nullptr;
+  if (wave >= A.n) return;
+  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+  // dst_offsets[q] in every lane (past the table: 0)
+  auto dst_off = [&](uint64_t q) __attribute__((always_inline)) -> uint64_t {
+    const uint64_t ob = uniform64((uint64_t)(uintptr_t)(A.dst_offsets + (q <= A.n ? q : 0)));
+    const __amdgpu_buffer_rsrc_t ro =
+        __builtin_amdgcn_make_buffer_rsrc((void *)ob, (short)0, q <= A.n ? 8 : 0, 0x00020000);
+    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(ro, 0, 0, 0);
+    return ((uint64_t)v.y << 32) | v.x;
+  };
+  const uint64_t doN = dst_off(A.n);
+
+  struct Ahead {
+    uint64_t f0, f1;
+  };
+  auto first_pair = [&](uint64_t q, Ahead &h) __attribute__((always_inline)) {
+    h.f0 = h.f1 = 0;
+    if (q < A.n) {
+      h.f0 = first[q];
+      h.f1 = first[q + 1];
+    }
+  };
+  auto packet = [&](PackPkt &P, uint64_t q, const Ahead &h) __attribute__((always_inline)) {
+    const uint64_t nv = h.f1 >= h.f0 ? h.f1 - h.f0 : 0;
+    P.g0 = h.f0;
+    P.nv = nv < 0xFFFFFFFFull ? (uint32_t)nv : 0xFFFFFFFFu;
+    P.o0 = dst_off(q < A.n ? q : A.n + 1);
+    P.o1 = dst_off(q < A.n ? q + 1 : A.n + 1);
+    const uint64_t base = uniform64((uint64_t)(uintptr_t)(views_ + h.f0));
+    const __amdgpu_buffer_rsrc_t r = rsrc_at(base, base + 16u * (P.nv < 64u ? P.nv : 64u));
+    const uint4 v = bld16(r, 16u * lane, false);
+    P.blo = v.x;
+    P.bhi = v.y;
+    P.len = v.w ? 0xFFFFFFFFu : v.z;
+    const uint32_t own = lead && q < A.n ? 0u : kOOB;
+    const uint64_t ab = uniform64(have_addrs ? (uint64_t)(uintptr_t)(addrs + 8 * q) : 0ull);
+    const uint64_t ib = uniform64(have_initial ? (uint64_t)(uintptr_t)(initial_arr + q) : 0ull);
+    const __amdgpu_buffer_rsrc_t ra =
+        __builtin_amdgcn_make_buffer_rsrc((void *)ab, (short)0, have_addrs ? 8 : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ri =
+        __builtin_amdgcn_make_buffer_rsrc((void *)ib, (short)0, have_initial ? 2 : 0, 0x00020000);
+    const u32x2 sab = __builtin_amdgcn_raw_buffer_load_b64(ra, (int)own, 0, 0);
+    const uint16_t sin = __builtin_amdgcn_raw_buffer_load_b16(ri, (int)own, 0, 0);
+    P.sa = sab.x;
+    P.sb = sab.y;
+    P.si = have_initial ? (uint32_t)sin : A.initial;
+  };
+  // Where packet P goes, in every lane.
+  auto dst_of = [&](const PackPkt &P) __attribute__((always_inline)) -> yu::IovPackDst {
+    return {(uint64_t)(uintptr_t)A.dst + P.o0, yu::iov_pack_room(P.o0, P.o1, doN)};
+  };
+
+  uint64_t wp = wave;
+  Ahead ff;
+  PackPkt cur, nx;
+  {
+    Ahead a, b;
+    first_pair(wp, a);
+    first_pair(wp + nwave, b);
+    first_pair(wp + 2 * nwave, ff);
+    packet(cur, wp, a);
+    packet(nx, wp + nwave, b);
+  }
+  yu::IovWalk W;
+  yu::iov_walk_reset(W);
+  uint32_t vi = 0;
+  int32_t vpk = 0;  // yu::iov_pack_view of the walk's current view
+
+  auto next_view = [&]() __attribute__((always_inline)) {
+    while (yu::iov_walk_done(W) && vi < cur.nv) {
+      uint64_t b;
+      uint32_t l;
+      if (vi < 64u) {
+        b = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)cur.bhi, (int)vi) << 32) |
+            (uint32_t)__builtin_amdgcn_readlane((int)cur.blo, (int)vi);
+        l = (uint32_t)__builtin_amdgcn_readlane((int)cur.len, (int)vi);
+      } else {
+        const uint64_t vl = views[cur.g0 + vi].len;
+        b = (uint64_t)(uintptr_t)views[cur.g0 + vi].base;
+        l = vl < 0xFFFFFFFFull ? (uint32_t)vl : 0xFFFFFFFFu;
+      }
+      vpk = yu::iov_pack_view(b, W.off);
+      yu::iov_walk_view(W, b, l, tx, f);
+      ++vi;
+    }
+  };
+  auto produce = [&](uint32_t (&info)[U], int32_t (&po)[U], yu::IovPackDst &D, uint4 (&c)[U], PackFin &fin)
+                     __attribute__((always_inline)) {
+    D = dst_of(cur);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      next_view();
+      po[u] = yu::iov_pack_po(vpk, W.w, lane);
+      yu::IovSlot S;
+      yu::iov_walk_slot(W, S);
+      info[u] = S.info;
+      const uint32_t lim = yu::iov_lim(S.info);
+      const uint64_t base = uniform64(S.base);
+      const __amdgpu_buffer_rsrc_t r = rsrc_at(base, base + lim);
+      const uint32_t cr = 16u * lane;
+      c[u] = bld16(r, cr < lim ? cr : kOOB, NT == 1 || (NT == 2 && u != 0));
+    }
+    next_view();
+    fin.last = yu::iov_walk_done(W) && vi >= cur.nv;
+    if (fin.last) {
+      const uint32_t bad = W.over | (W.off > D.room ? 1u : 0u);
+      fin.len = lead ? (W.off | (bad << 31)) : 0u;
+      fin.sa = cur.sa;
+      fin.sb = cur.sb;
+      fin.si = cur.si;
+      wp += nwave;
+      cur = nx;
+      packet(nx, wp + nwave, ff);
+      first_pair(wp + 2 * nwave, ff);
+      yu::iov_walk_reset(W);
+      vi = 0;
+      vpk = 0;
+    }
+  };
+
+  const PackStore st;
+  uint64_t p = in_vgpr(wave);  // the packet being summed
+  uint32_t accA = 0, accB = 0;
+  uint32_t jA = 0, jB = 0;
+  uint32_t cprev = 0;          // lane 63: the last source dword of the slot before
+  uint64_t fa0 = 0, fa1 = 0;   // lead lane: where the held-back field bytes go (0: not held)
+  uint32_t fb0 = 0, fb1 = 0;   // ... and the bytes as read
+  // One step: issue its loads, then sum and store it and finish its packet if it
+  // ends one (false: the wave's last packet is done). Unlike k_iov the next
+  // step's loads are not in flight meanwhile: the second set of registers that
+  // takes is what the store side lives in, and the other waves cover the wait.
+  auto step = [&](uint32_t (&ic)[U], int32_t (&pc)[U], yu::IovPackDst &Dc, uint4 (&c)[U], PackFin &fc)
+                  __attribute__((always_inline)) -> bool {
+    produce(ic, pc, Dc, c, fc);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint32_t info = ic[u];
+      const uint32_t lim = yu::iov_lim(info);
+      if (lim == 0) continue;
+      uint32_t t = 0;
+      if (lim >= yu::kIovSlot && !(info & yu::kIovFirst)) {
+        t = sum_full<false>(c[u], 0u, 0u);
+      } else {
+        const uint32_t hm = yu::iov_head_mask(info);
+        const uint32_t cr = 16u * lane;
+        t = yu::iov_add(yu::iov_dword(c[u].x, cr, lim, hm), t);
+        t = yu::iov_add(yu::iov_dword(c[u].y, cr + 4u, lim, hm), t);
+        t = yu::iov_add(yu::iov_dword(c[u].z, cr + 8u, lim, hm), t);
+        t = yu::iov_add(yu::iov_dword(c[u].w, cr + 12u, lim, hm), t);
+      }
+      const bool swap = (info & yu::kIovSwap) != 0;
+      yu::IovPackPlan P;
+      yu::iov_pack_plan(P, info, Dc, pc[u], lane);
+      int32_t fq0 = -1, fq1 = -1;
+      if (info & (yu::kIovF0 | yu::kIovF1)) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          if (yu::iov_has_field(info, k)) {
+            const uint32_t q = yu::iov_field_q(info, k);
+            const uint32_t word = (uint32_t)__builtin_amdgcn_readlane(
+                (int)pick_dword(c[u], (q >> 2) & 3u), (int)(q >> 4));
+            const uint32_t term = yu::iov_field_term(word, q);
+            jA += (lead && swap) ? term : 0u;
+            jB += (lead && !swap) ? term : 0u;
+            // held back when it fits the room (the same answer in every lane)
+            const bool held = yu::iov_pack_field_held(P, q, lane);
+            const uint32_t byte = (word >> (8u * (q & 3u))) & 0xFFu;
+            if (k == 0) {
+              fq0 = held ? (int32_t)q : -1;
+              fa0 = lead && held ? yu::iov_pack_field_addr(P, q, lane) : fa0;
+              fb0 = byte;
+            } else {
+              fq1 = held ? (int32_t)q : -1;
+              fa1 = lead && held ? yu::iov_pack_field_addr(P, q, lane) : fa1;
+              fb1 = byte;
+            }
+          }
+        }
+      }
+      // the source dword before the lane's own: the neighbour's last, and for lane 0
+      // the last of the slot before, which lane 63 offers in place of its own
+      const uint32_t prev = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(4u * ((lane - 1u) & 63u)),
+                                                                   (int)(lead ? cprev : c[u].w));
+      yu::iov_pack_lane(st, P, lane, c[u].x, c[u].y, c[u].z, c[u].w, prev, fq0, fq1);
+      cprev = c[u].w;
+      accA += swap ? t : 0u;
+      accB += swap ? 0u : t;
+    }
+    if (!fc.last) return true;
+    uint32_t sA = group_total<64>(accA), sB = group_total<64>(accB);
+    if (lead) {
+      const uint32_t len = fc.len & 0x7FFFFFFFu;
+      const bool fld = tx && len >= f + 2u;
+      if (fld) {
+        sA -= jA;
+        sB -= jB;
+      }
+      const uint32_t r = yu::iov_value(mode, yu::iov_residue(sA, sB), len, have_addrs, fc.sa,
+                                       fc.sb, fc.si);
+      if (A.out) A.out[p] = (uint16_t)r;
+      if (tx) {
+        const bool put = FILL && fld && !(fc.len >> 31);  // binary.BigEndian.PutUint16 into the copy
+        yu::iov_pack_field_store(st, fa0, fa1, put ? r >> 8 : fb0, put ? r & 0xFFu : fb1);
+      }
+    }
+    accA = accB = jA = jB = 0;
+    fa0 = fa1 = 0;
+    p += nwave;
+    return uniform64(p) < A.n;
+  };
+
+  uint32_t i0[U];
+  int32_t p0[U];
+  yu::IovPackDst d0;
+  uint4 c0[U];
+  PackFin n0;
+  while (step(i0, p0, d0, c0, n0)) {
+  }
+}
+
+// ---------------------------------------------------------------------
 // Host side: launch. Which kernel, form, load policy and grid a batch gets is
 // yu::plan's decision (yucsum_plan.cpp); here are the functions it names.
 // ---------------------------------------------------------------------
@@ -2786,6 +3095,43 @@ int batch_iov_datagram(const yu_iovec *views, const uint64_t *first_iov, uint64_
   return hip_status(hipGetLastError());
 }
 
+// The packing form: the same tables, the packed copy besides (dst, dst_offsets).
+typedef void (*PackFn)(const yu_iovec *, const uint64_t *, const uint16_t *, const uint8_t *, PackArgs);
+const PackFn kPackFns[yu::kIovPackKernelCount][3] = {
+    {k_pack<4, 0, false>, k_pack<4, 1, false>, k_pack<4, 2, false>},
+    {k_pack<4, 0, true>, k_pack<4, 1, true>, k_pack<4, 2, true>},
+};
+
+int pack_iov(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode,
+             const uint16_t *initial_arr, uint16_t initial, const uint8_t *addrs, uint8_t *dst,
+             const uint64_t *dst_offsets, uint16_t *out, bool fill, void *stream) {
+  if (mode < 0 || mode >= YU_MODE_COUNT) return YU_EINVAL;     // EINVAL:mode
+  if (fill && !yu::iov_mode_tx(mode)) return YU_EINVAL;         // EINVAL:fill-mode (no field, or a mode this form refuses)
+  if (!yu::iov_mode_ok(mode)) return YU_EINVAL;                 // EINVAL:mode (IPV4, VERIFY_IPV4, VERIFY_RX, TX_DATAGRAM parse headers)
+  if (!out && !fill && n) return YU_EINVAL;                     // EINVAL:out
+  if (initial_arr && !aligned(initial_arr, 2)) return YU_EINVAL;  // EINVAL:side-align
+  if (addrs && !aligned(addrs, 4)) return YU_EINVAL;              // EINVAL:side-align
+  if (out && !aligned(out, 2)) return YU_EINVAL;                  // EINVAL:side-align
+  if (n == 0) return YU_OK;
+  if (!first_iov || !aligned(first_iov, 8) || !aligned(views, 8)) return YU_EINVAL;  // EINVAL:offsets
+  if (!dst_offsets || !aligned(dst_offsets, 8)) return YU_EINVAL;                   // EINVAL:offsets
+  if (!views || !dst) return YU_EINVAL;                                             // EINVAL:data
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return hip_status(e);
+  const yu::IovPlan p = yu::plan_iov_pack(n, mode, fill, cu_count(dev), yu::env_knobs());
+  PackArgs a;
+  a.out = out;
+  a.dst = dst;
+  a.dst_offsets = dst_offsets;
+  a.n = n;
+  a.initial = initial;
+  a.mode = mode;
+  hipLaunchKernelGGL(kPackFns[p.kernel - yu::k_pack4][p.policy], dim3(p.blocks), dim3(256), 0,
+                     (hipStream_t)stream, views, first_iov, initial_arr, addrs, a);
+  return hip_status(hipGetLastError());
+}
+
 // Completion signal for the host path's direct mode (yucsum_internal.h):
 // stored after the work before it on the stream, with system-scope release,
 // into coherent pinned host memory.
@@ -2872,6 +3218,24 @@ const char *yu_iov_datagram_variant_n(int mode, uint64_t n, int fill) {
   if (mode < 0 || mode >= YU_MODE_COUNT || !yu::iov_dg_mode_ok(mode)) return "";
   if (fill && !yu::iov_dg_mode_tx(mode)) return "";
   return yu::plan_iov(n, mode, fill != 0, 256, yu::env_knobs()).name;
+}
+
+int yu_csum_pack_iov(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode,
+                     const uint16_t *initial_arr, uint16_t initial, const uint8_t *addrs, uint8_t *dst,
+                     const uint64_t *dst_offsets, uint16_t *out, void *stream) {
+  return pack_iov(views, first_iov, n, mode, initial_arr, initial, addrs, dst, dst_offsets, out, false, stream);
+}
+
+int yu_csum_pack_fill_iov(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode,
+                          const uint16_t *initial_arr, uint16_t initial, const uint8_t *addrs, uint8_t *dst,
+                          const uint64_t *dst_offsets, uint16_t *out, void *stream) {
+  return pack_iov(views, first_iov, n, mode, initial_arr, initial, addrs, dst, dst_offsets, out, true, stream);
+}
+
+const char *yu_iov_pack_variant_n(int mode, uint64_t n, int fill) {
+  if (mode < 0 || mode >= YU_MODE_COUNT || !yu::iov_mode_ok(mode)) return "";
+  if (fill && !yu::iov_mode_tx(mode)) return "";
+  return yu::plan_iov_pack(n, mode, fill != 0, 256, yu::env_knobs()).name;
 }
 
 const char *yu_uniform_variant(uint64_t stride, uint32_t len, int mode,

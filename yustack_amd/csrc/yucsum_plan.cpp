@@ -307,4 +307,13 @@ IovPlan plan_iov(uint64_t n, int mode, bool fill, int cus, const Knobs &k) {
   return p;
 }
 
+// k_pack: k_iov's grid and load policy (the source side is k_iov's), its own
+// kernels and names.
+IovPlan plan_iov_pack(uint64_t n, int mode, bool fill, int cus, const Knobs &k) {
+  IovPlan p = plan_iov(n, mode, fill, cus, k);
+  p.kernel = fill ? k_pack4_fill : k_pack4;
+  p.name = fill ? "k_pack<4,fill>" : "k_pack<4>";
+  return p;
+}
+
 }  // namespace yu

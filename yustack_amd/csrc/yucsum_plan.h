@@ -176,7 +176,12 @@ Plan plan(const Shape &s, int cus, const Knobs &k);
 // The scatter-gather device calls (yu_csum_batch_iov / yu_csum_fill_iov) have a
 // plan of their own: one kernel family, k_iov (yucsum_iov.h), which is not one
 // of YU_KERNELS because no uniform or ragged batch ever takes it.
-enum IovKernel : uint8_t { k_iov4, k_iov4_fill, k_iov4_dg, k_iov4_dg_fill, kIovKernelCount };
+enum IovKernel : uint8_t {
+  k_iov4, k_iov4_fill, k_iov4_dg, k_iov4_dg_fill, kIovKernelCount,
+  // k_pack (yucsum_iov_pack.h), the packing calls' family: rows of its own table
+  k_pack4 = kIovKernelCount, k_pack4_fill, kIovPackEnd
+};
+constexpr int kIovPackKernelCount = kIovPackEnd - k_pack4;
 struct IovPlan {
   IovKernel kernel;
   uint8_t policy;  // load-policy slot: 0 plain, 1 nt, 2 plain for a step's first slot, nt for the rest
@@ -186,6 +191,9 @@ struct IovPlan {
 // mode: one of the modes the form takes (yu::iov_mode_ok), or one of the whole-
 // datagram modes of yu_csum_batch_iov_datagram (yu::iov_dg_mode_ok): the dg kernels.
 IovPlan plan_iov(uint64_t n, int mode, bool fill, int cus, const Knobs &k);
+// The packing calls (yu_csum_pack_iov / yu_csum_pack_fill_iov): k_pack on
+// plan_iov's grid and load policy. mode: one yu::iov_mode_ok takes.
+IovPlan plan_iov_pack(uint64_t n, int mode, bool fill, int cus, const Knobs &k);
 
 }  // namespace yu
 #pragma GCC visibility pop
