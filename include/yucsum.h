@@ -528,8 +528,8 @@ int yu_csum_fill_iov_datagram(const yu_iovec *views, const uint64_t *first_iov,
  * for yu_csum_batch_iov; [offsets]: also dst_offsets == NULL or not 8-byte
  * aligned; [data]: views == NULL or dst == NULL with n > 0.
  *
- * IPV4, VERIFY_IPV4, VERIFY_RX and TX_DATAGRAM are not taken yet: run
- * yu_csum_fill_ragged(TX_DATAGRAM) on the packed copy. */
+ * IPV4, VERIFY_IPV4, VERIFY_RX and TX_DATAGRAM are [mode] here:
+ * yu_csum_pack_iov_datagram / yu_csum_pack_fill_iov_datagram below take them. */
 int yu_csum_pack_iov(const yu_iovec *views, const uint64_t *first_iov,
                      uint64_t n, int mode, const uint16_t *initial_arr,
                      uint16_t initial, const uint8_t *addrs, uint8_t *dst,
@@ -538,6 +538,63 @@ int yu_csum_pack_fill_iov(const yu_iovec *views, const uint64_t *first_iov,
                           uint64_t n, int mode, const uint16_t *initial_arr,
                           uint16_t initial, const uint8_t *addrs, uint8_t *dst,
                           const uint64_t *dst_offsets, uint16_t *out, void *stream);
+
+/* Scatter-gather device batches of whole IPv4 datagrams, verified or filled
+ * and packed in one pass: what yu_csum_batch_iov_datagram does, and the copy of
+ * yu_csum_pack_iov besides. The sending side hands writev a header view and a
+ * payload view and needs both fields in the wire image (TX_DATAGRAM, fill); a
+ * received VectorisedView is concatenated and then checked (VERIFY_RX). One
+ * read of the views, one write of the copy.
+ *
+ * Call discipline, layout, tables, `dst`, `dst_offsets`, slack, room and "out
+ * of contract" are yu_csum_pack_iov's, word for word: device CSR tables and
+ * bases, `dst_offsets` n + 1 DEVICE uint64 values, 8-byte aligned, `dst` a
+ * DEVICE pointer of any alignment that overlaps nothing the call reads;
+ * asynchronous on `stream`, no allocation, no synchronisation,
+ * graph-capturable, YU_ENODEV without a device, n == 0 a no-op returning YU_OK
+ * after the mode checks. There are no side arrays.
+ *
+ * Modes: IPV4, VERIFY_IPV4, VERIFY_RX, TX_DATAGRAM; every other mode is [mode]
+ * (yu_csum_pack_iov takes those). The fill form takes IPV4 and TX_DATAGRAM
+ * ([fill-mode]). `out` holds n * YU_MODE_OUTPUTS(mode) values and may be NULL
+ * in the fill form.
+ *
+ * Value: out is exactly yu_csum_batch_iov_datagram's, in every case that call
+ * defines (packets shorter than 20 bytes, 0 included; any IHL; TotalLength()
+ * below, at or past the bytes present; bytes past TotalLength(); other
+ * protocols; segments shorter than their fixed header).
+ *
+ * Copy: all len_i bytes of packet i are stored at dst[dst_offsets[i], ...): the
+ * header, bytes outside [HeaderLength(), TotalLength()) and bytes past
+ * TotalLength() included, for invalid datagrams as for valid ones. The copy
+ * does not depend on the parse.
+ *
+ * Field bytes in the copy: yu_csum_pack_iov_datagram copies them as read.
+ * yu_csum_pack_fill_iov_datagram stores exactly the fields yu_csum_fill_ragged
+ * would store on the packed copy (yu_csum_fill_iov_datagram's rule: bytes
+ * 10..11, and the transport field at HeaderLength() + {6 UDP, 16 TCP, 2 ICMP}),
+ * big-endian, iff the packet is in contract; every other byte, and the field
+ * bytes of a datagram that gets no field, are copied as read. An out-of-contract
+ * packet's field bytes are copied as read where they fit its room. No source
+ * view is ever written, so views may be shared between packets: one header
+ * template named by many packets gets its own fields in each copy. Every byte
+ * of dst is stored by exactly one store of the call, never a
+ * read-modify-write: the fill form holds bytes 10..11 and the transport
+ * field's bytes back until the packet is done (TotalLength() <= len is known
+ * only then) and stores them once, the value or the byte as read.
+ *
+ * Reads: only dwords that hold bytes of the views named (all of them: the copy
+ * takes every byte).
+ *
+ * YU_EINVAL (Preconditions above): [mode], [fill-mode], [out], [side-align]
+ * (out), [offsets] (first_iov, views, dst_offsets), [data] (views == NULL or
+ * dst == NULL with n > 0), as for yu_csum_pack_iov. */
+int yu_csum_pack_iov_datagram(const yu_iovec *views, const uint64_t *first_iov,
+                              uint64_t n, int mode, uint8_t *dst,
+                              const uint64_t *dst_offsets, uint16_t *out, void *stream);
+int yu_csum_pack_fill_iov_datagram(const yu_iovec *views, const uint64_t *first_iov,
+                                   uint64_t n, int mode, uint8_t *dst,
+                                   const uint64_t *dst_offsets, uint16_t *out, void *stream);
 
 /* Host-memory field writer: the matching yu_csum_batch_host_* call (TX modes
  * UDP/TCP/IPV4/ICMP/TX_DATAGRAM only), then each result stored big-endian into the
@@ -674,6 +731,9 @@ const char *yu_iov_variant_n(int mode, uint64_t n, int fill);
 const char *yu_iov_datagram_variant_n(int mode, uint64_t n, int fill);
 /* The same for the packing calls (fill != 0: yu_csum_pack_fill_iov). */
 const char *yu_iov_pack_variant_n(int mode, uint64_t n, int fill);
+/* The same for the packing whole-datagram calls (fill != 0:
+ * yu_csum_pack_fill_iov_datagram). */
+const char *yu_iov_pack_datagram_variant_n(int mode, uint64_t n, int fill);
 
 #ifdef __cplusplus
 }

@@ -302,6 +302,25 @@ inline void PackFillIov(const yu_iovec *views, const uint64_t *first_iov, uint64
   if (rc) throw Error(rc, "yu_csum_pack_fill_iov");
 }
 
+// The packing form for whole IPv4 datagrams (IPV4, VERIFY_IPV4, VERIFY_RX,
+// TX_DATAGRAM; out: n * YU_MODE_OUTPUTS(m) values): the results of
+// yu_csum_batch_iov_datagram and every byte of each packet at dst[dst_offsets[i] ...] in one pass.
+// PackFillIovDatagram (IPV4, TX_DATAGRAM) gives the copy the fields FillRagged
+// would store on it; the views are never written.
+inline void PackIovDatagram(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, Mode m,
+                            uint8_t *dst, const uint64_t *dst_offsets, uint16_t *out,
+                            void *stream = nullptr) {
+  int rc = yu_csum_pack_iov_datagram(views, first_iov, n, m, dst, dst_offsets, out, stream);
+  if (rc) throw Error(rc, "yu_csum_pack_iov_datagram");
+}
+
+inline void PackFillIovDatagram(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, Mode m,
+                                uint8_t *dst, const uint64_t *dst_offsets, uint16_t *out = nullptr,
+                                void *stream = nullptr) {
+  int rc = yu_csum_pack_fill_iov_datagram(views, first_iov, n, m, dst, dst_offsets, out, stream);
+  if (rc) throw Error(rc, "yu_csum_pack_fill_iov_datagram");
+}
+
 // Host buffers in, host results out (pinned staging + pipelined copies, or
 // the direct path for bursts up to 4 MiB). Here `Side` holds HOST pointers.
 // A device list shards the batch over several GPUs (the *_multi calls).

@@ -20,7 +20,15 @@ Whole-datagram workloads (yu_csum_batch_iov_datagram / yu_csum_fill_iov_datagram
 1500-byte TCP datagrams, each a 40-byte header view (IPv4 + TCP header) and a 1460-byte
 payload view; rx1500 is VERIFY_RX, tx1500 TX_DATAGRAM in place. The alternatives are the
 same four, with the ragged-form modes on the packed copy (tx1500's pack+sum leaves its
-fields in the copy: scattering them back to the views is not charged to it).
+fields in the copy: scattering them back to the views is not charged to it), and two that
+deliver the packed datagrams as well as the results:
+
+  pack_fused        yu_csum_pack_iov_datagram / yu_csum_pack_fill_iov_datagram into a
+                    preallocated dst: one launch
+  pack_then_ragged  yu_csum_pack_iov(RAW) into a preallocated dst, then yu_csum_batch_ragged /
+                    yu_csum_fill_ragged on the copy: what took two launches before
+
+Their results and dst bytes are asserted equal before timing.
 
 The pools rotate over --sets copies (more than 2 GiB in all for the MTU workload), so
 no launch finds its bytes in the Infinity Cache. Prints one JSON line per workload.
@@ -178,7 +186,26 @@ def run_datagram(name, n, launches, sets, dev):
     def floor(k):
         batch.checksum_uniform(packed[k].view(-1), ln, ln, n, mode, out=out, fill=fill)
 
-    alts = {"iov": iov, "iov_py": iov_py, "pack+sum": pack_sum, "packed": floor}
+    dst = torch.zeros(n * ln, dtype=torch.uint8, device=dev)
+    dst2 = torch.zeros(n * ln, dtype=torch.uint8, device=dev)
+    dst_offsets = torch.arange(n + 1, device=dev) * ln
+    raw = torch.zeros(n, dtype=torch.uint16, device=dev)
+    pack_call = L.yu_csum_pack_fill_iov_datagram if fill else L.yu_csum_pack_iov_datagram
+    ragged_call = L.yu_csum_fill_ragged if fill else L.yu_csum_batch_ragged
+
+    def pack_fused(k):
+        _lib.check(pack_call(tables[k].data_ptr(), first.data_ptr(), n, m, dst.data_ptr(), dst_offsets.data_ptr(),
+                             out.data_ptr(), stream), "pack_iov_datagram")
+
+    def pack_then_ragged(k):
+        _lib.check(L.yu_csum_pack_iov(tables[k].data_ptr(), first.data_ptr(), n, batch.MODES["raw"], None, 0, None,
+                                      dst2.data_ptr(), dst_offsets.data_ptr(), raw.data_ptr(), stream),
+                   "yu_csum_pack_iov")
+        _lib.check(ragged_call(dst2.data_ptr(), dst_offsets.data_ptr(), n, m, None, 0, None, out.data_ptr(), stream),
+                   "ragged on the copy")
+
+    alts = {"iov": iov, "iov_py": iov_py, "pack+sum": pack_sum, "packed": floor, "pack_fused": pack_fused,
+            "pack_then_ragged": pack_then_ragged}
     # every alternative computes the same values, and they are the oracle's (the
     # fields a fill stores are taken as zero by the mode, so a second pass agrees)
     want = O.C().batch(packed[0].cpu().numpy().reshape(-1), m, stride=ln, length=ln, n=n, threads=16).reshape(-1)
@@ -186,6 +213,10 @@ def run_datagram(name, n, launches, sets, dev):
         out.zero_()
         fn(0)
         assert np.array_equal(out.cpu().numpy(), want), a
+    # the two packing alternatives leave the same bytes: the datagrams, in the fill
+    # workload with both fields in each (packed[0] got them from `packed` above)
+    assert torch.equal(dst, dst2), "pack_fused and pack_then_ragged leave different bytes"
+    assert torch.equal(dst, packed[0].view(-1)), "pack_fused: dst is not the packed datagrams"
     times = {a: [] for a in alts}
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in alts]
     for it in range(launches + 3):
@@ -210,6 +241,11 @@ def run_datagram(name, n, launches, sets, dev):
         "iov_vs_floor": round(med["iov"] / med["packed"], 3),
         "iov_algorithmic_bytes": alg,
         "iov_fraction_of_hbm_peak": round(alg / (med["iov"] * 1e-6) / PEAK, 3),
+        "pack_variant": batch.iov_pack_datagram_variant(mode, n, fill),
+        "pack_fused_vs_pack_then_ragged": round(med["pack_fused"] / med["pack_then_ragged"], 3),
+        "pack_fused_vs_pack_sum": round(med["pack_fused"] / med["pack+sum"], 3),
+        # one read of the views and tables, one write of the copy
+        "pack_fused_fraction_of_hbm_peak": round((alg + n * (ln + 16)) / (med["pack_fused"] * 1e-6) / PEAK, 3),
     }
     print(json.dumps(res), flush=True)
     return res

@@ -19,6 +19,7 @@ EXPORTS = (
     "yu_csum_fill_uniform", "yu_csum_fill_ragged", "yu_csum_batch_iov", "yu_csum_fill_iov",
     "yu_csum_batch_iov_datagram", "yu_csum_fill_iov_datagram", "yu_iov_datagram_variant_n",
     "yu_csum_pack_iov", "yu_csum_pack_fill_iov", "yu_iov_pack_variant_n",
+    "yu_csum_pack_iov_datagram", "yu_csum_pack_fill_iov_datagram", "yu_iov_pack_datagram_variant_n",
     "yu_csum_batch_host_uniform", "yu_csum_batch_host_ragged", "yu_csum_batch_host_iov",
     "yu_csum_batch_host_uniform_multi", "yu_csum_batch_host_ragged_multi",
     "yu_csum_batch_host_iov_multi",
@@ -140,6 +141,12 @@ def lib() -> ctypes.CDLL:
         f.argtypes = [vp, vp, u64, i32, vp, u16, vp, vp, vp, vp, vp]
     L.yu_iov_pack_variant_n.restype = c.c_char_p
     L.yu_iov_pack_variant_n.argtypes = [i32, u64, i32]
+    for name in ("yu_csum_pack_iov_datagram", "yu_csum_pack_fill_iov_datagram"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, vp, u64, i32, vp, vp, vp, vp]
+    L.yu_iov_pack_datagram_variant_n.restype = c.c_char_p
+    L.yu_iov_pack_datagram_variant_n.argtypes = [i32, u64, i32]
     L.yu_host_contexts.restype = i32
     L.yu_host_contexts.argtypes = []
     L.yu_host_staging_bytes.restype = u64

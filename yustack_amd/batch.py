@@ -2,7 +2,8 @@
 
 Thin Python front end over the C ABI's batched entry points
 (``yu_csum_batch_uniform`` / ``yu_csum_batch_ragged`` / ``yu_csum_batch_iov`` /
-``yu_csum_batch_iov_datagram`` / ``yu_csum_pack_iov`` / ``yu_csum_fill_*`` / ``yu_csum_batch_host_uniform``,
+``yu_csum_batch_iov_datagram`` / ``yu_csum_pack_iov`` / ``yu_csum_pack_iov_datagram`` / ``yu_csum_fill_*`` /
+``yu_csum_batch_host_uniform``,
 include/yucsum.h). PyTorch is used only for device
 memory and streams: the arithmetic happens in the hand-written gfx950 kernels of
 ``csrc/yucsum_kernels.hip``. There is no CPU fallback — without a HIP device every
@@ -310,6 +311,45 @@ def _overlaps(a: torch.Tensor, b: torch.Tensor) -> bool:
     return a0 < b1 and b0 < a1
 
 
+def _pack_dst(pools, dev, table, fi, n, view_len, dst, dst_offsets, validate: bool):
+    """``dst`` and ``dst_offsets`` of the packing calls: the tight offsets and a new
+    ``dst`` where they are not given, and the checks ``validate`` asks for. Returns
+    (dst, the offsets as int64)."""
+    if dst is not None:
+        _dev_u8(dst, "dst")
+        if dst.device != dev:
+            raise TypeError(f"dst must be on {dev}")
+        if any(_overlaps(dst, pool) for pool in pools):
+            raise ValueError("dst overlaps a pool")
+    need_len = dst_offsets is None or (validate and n > 0)
+    if need_len:  # the packets' lengths: sums of their views' lengths
+        nviews = view_len.numel()
+        ends = torch.zeros(nviews + 1, dtype=torch.int64, device=dev)
+        if nviews:
+            ends[1:] = torch.cumsum(table[:, 1].clamp(min=0), 0)
+        f = fi.clamp(0, nviews)
+        plen = (ends[f[1:]] - ends[f[:-1]]).clamp(min=0)
+    if dst_offsets is None:
+        do = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        do[1:] = torch.cumsum(plen, 0)
+    else:
+        do = _dev_index(dst_offsets, "dst_offsets", dev, n + 1)
+        if do.dtype != torch.int64 or do.data_ptr() % 8:
+            raise TypeError("dst_offsets must be 8-byte aligned")
+    if dst is None:
+        dst = torch.empty(max(int(do[-1].item()), 1), dtype=torch.uint8, device=dev)
+    if validate and n > 0:
+        room = do[1:] - do[:-1]
+        ok = torch.stack(((room >= 0).all() & (do[0] >= 0), (room >= plen).all(), do[-1] <= dst.numel())).tolist()
+        if not ok[0]:
+            raise ValueError("dst_offsets is not non-decreasing")
+        if not ok[1]:
+            raise ValueError("a packet has less room in dst than bytes")
+        if not ok[2]:
+            raise ValueError("dst_offsets run past dst")
+    return dst, do
+
+
 def pack_iov(pools, view_pool: torch.Tensor, view_off: torch.Tensor, view_len: torch.Tensor,
              first: torch.Tensor, mode="raw", *, initial: int = 0,
              initial_arr: torch.Tensor | None = None, addrs: torch.Tensor | None = None,
@@ -343,38 +383,7 @@ def pack_iov(pools, view_pool: torch.Tensor, view_off: torch.Tensor, view_len: t
     dev, table, fi, n = _iov_table(pools, view_pool, view_off, view_len, first, validate)
     initial_arr = _opt(initial_arr, torch.uint16, n, dev, "initial_arr")
     addrs = _opt(addrs, torch.uint8, 8 * n, dev, "addrs")
-    if dst is not None:
-        _dev_u8(dst, "dst")
-        if dst.device != dev:
-            raise TypeError(f"dst must be on {dev}")
-        if any(_overlaps(dst, pool) for pool in pools):
-            raise ValueError("dst overlaps a pool")
-    need_len = dst_offsets is None or (validate and n > 0)
-    if need_len:  # the packets' lengths: sums of their views' lengths
-        nviews = view_len.numel()
-        ends = torch.zeros(nviews + 1, dtype=torch.int64, device=dev)
-        if nviews:
-            ends[1:] = torch.cumsum(table[:, 1].clamp(min=0), 0)
-        f = fi.clamp(0, nviews)
-        plen = (ends[f[1:]] - ends[f[:-1]]).clamp(min=0)
-    if dst_offsets is None:
-        do = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-        do[1:] = torch.cumsum(plen, 0)
-    else:
-        do = _dev_index(dst_offsets, "dst_offsets", dev, n + 1)
-        if do.dtype != torch.int64 or do.data_ptr() % 8:
-            raise TypeError("dst_offsets must be 8-byte aligned")
-    if dst is None:
-        dst = torch.empty(max(int(do[-1].item()), 1), dtype=torch.uint8, device=dev)
-    if validate and n > 0:
-        room = do[1:] - do[:-1]
-        ok = torch.stack(((room >= 0).all() & (do[0] >= 0), (room >= plen).all(), do[-1] <= dst.numel())).tolist()
-        if not ok[0]:
-            raise ValueError("dst_offsets is not non-decreasing")
-        if not ok[1]:
-            raise ValueError("a packet has less room in dst than bytes")
-        if not ok[2]:
-            raise ValueError("dst_offsets run past dst")
+    dst, do = _pack_dst(pools, dev, table, fi, n, view_len, dst, dst_offsets, validate)
     if out is None:
         out = torch.empty(max(n, 1), dtype=torch.uint16, device=dev)[:n]
     else:
@@ -387,6 +396,49 @@ def pack_iov(pools, view_pool: torch.Tensor, view_off: torch.Tensor, view_len: t
                              _ptr(addrs), dst.data_ptr(), do.data_ptr(), out.data_ptr() if n else None, s))
     out.iov_table = (table, fi, do)
     return out, dst, (do if dst_offsets is None else dst_offsets)
+
+
+def pack_iov_datagrams(pools, view_pool: torch.Tensor, view_off: torch.Tensor, view_len: torch.Tensor,
+                       first: torch.Tensor, mode="verify_rx", *, dst: torch.Tensor | None = None,
+                       dst_offsets: torch.Tensor | None = None, out: torch.Tensor | None = None,
+                       stream: torch.cuda.Stream | None = None, fill: bool = False, validate: bool = True):
+    """Whole IPv4 datagrams held as scatter-gather device packets, verified or filled
+    and packed into one buffer in one pass (yu_csum_pack_iov_datagram /
+    yu_csum_pack_fill_iov_datagram). The layout, the table, the modes and ``out`` are
+    :func:`checksum_iov_datagrams`'s (IPV4, VERIFY_IPV4, VERIFY_RX, TX_DATAGRAM, no side
+    arrays); ``dst``, ``dst_offsets``, ``validate`` and ``stream`` are :func:`pack_iov`'s.
+    Returns ``(out, dst, dst_offsets)``: every byte of packet i lies at
+    ``dst[dst_offsets[i] : dst_offsets[i] + len_i]``, whatever its header says, and
+    ``out`` is :func:`checksum_iov_datagrams`'s. ``fill=True`` (IPV4, TX_DATAGRAM) gives
+    the copy the fields :func:`checksum_ragged` with ``fill=True`` would store on it;
+    the pools are never written, so one header template may serve many packets."""
+    m = _mode(mode)
+    if m not in IOV_DATAGRAM_MODES:
+        raise ValueError("pack_iov_datagrams takes ipv4, verify_ipv4, verify_rx and tx_datagram")
+    if fill and m not in IOV_DATAGRAM_FILL_MODES:
+        raise ValueError("fill=True takes ipv4 or tx_datagram")
+    pools = list(pools)
+    dev, table, fi, n = _iov_table(pools, view_pool, view_off, view_len, first, validate)
+    dst, do = _pack_dst(pools, dev, table, fi, n, view_len, dst, dst_offsets, validate)
+    k = outputs(m)
+    if out is None:
+        out = torch.empty(max(n * k, 1), dtype=torch.uint16, device=dev)[:n * k]
+    else:
+        _opt(out, torch.uint16, n * k, dev, "out")
+    if stream is not None:
+        do.record_stream(stream)
+        dst.record_stream(stream)
+    _iov_call("yu_csum_pack_fill_iov_datagram" if fill else "yu_csum_pack_iov_datagram", dev, table, fi, stream,
+              lambda f, s: f(table.data_ptr(), fi.data_ptr(), n, m, dst.data_ptr(), do.data_ptr(),
+                             out.data_ptr() if n else None, s))
+    out.iov_table = (table, fi, do)
+    return out, dst, (do if dst_offsets is None else dst_offsets)
+
+
+def iov_pack_datagram_variant(mode="verify_rx", n: int = 1 << 20, fill: bool = False) -> str:
+    """Name of the kernel the packing whole-datagram calls launch ("" for a mode
+    they refuse)."""
+    return lib().yu_iov_pack_datagram_variant_n(_mode(mode), n, 1 if fill else 0).decode()
 
 
 def iov_pack_variant(mode="raw", n: int = 1 << 20, fill: bool = False) -> str:

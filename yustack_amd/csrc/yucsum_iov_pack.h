@@ -181,6 +181,114 @@ YU_IOV_FN void iov_pack_lane(St &st, const IovPackPlan &P, uint32_t L, uint32_t 
   }
 }
 
+// ---------------------------------------------------------------------
+// Whole IPv4 datagrams, packed (yu_csum_pack_iov_datagram /
+// yu_csum_pack_fill_iov_datagram, the kernel k_pack_dg): the header gather, the
+// parse and the epilogue are the datagram kind's (yucsum_iov.h, last section),
+// the store side is the one above. The two do not agree on which bytes they
+// want: the copy takes every byte of the packet, the sums the header (from the
+// gathered lanes) and the window [lo, hi) = [HL, TL) only. So the walk is the
+// plain one over whole views, and the window is applied to the sum alone, by
+// the slot's place in the packet: a slot inside the window is summed as ever,
+// one outside it is not summed, one that straddles lo or hi has each dword's
+// bytes masked by packet offset first. The sum stays a sum of the segment's
+// own bytes.
+//
+// With whole views the transport field at f = HL + {6, 16, 2} <= 76 no longer
+// lies within 17 bytes of its view's start, so its window byte q (<= 3 + 76)
+// needs 7 bits of the info word: iov_walk_view already puts them there (bits
+// 23..29, nothing above them is used) and iov_field_q7 reads them. A packet
+// offset below 78 lies in the first slot of its view, so do all four bytes
+// that are held back in the fill form: 10 and 11 (IPv4's field, whose bytes as
+// read are the gather's) and f, f + 1.
+// ---------------------------------------------------------------------
+YU_IOV_FN uint32_t iov_field_q7(uint32_t info, int k) {
+  const uint32_t q = (info >> kIovQShift) & 127u;
+  return q + ((k && (info & kIovF0)) ? 1u : 0u);
+}
+
+// How the slot whose window byte 0 is packet offset p0 lies to the window
+// [lo, hi) (wave-uniform): 0 no byte of it is summed, 1 all of them, 2 some.
+YU_IOV_FN int iov_pack_dg_span(uint32_t info, int32_t p0, uint32_t lo, uint32_t hi) {
+  const uint32_t lim = iov_lim(info);
+  const int32_t s = (info & kIovFirst) ? (int32_t)((info >> kIovShShift) & 3u) : 0;
+  const int32_t a = p0 + s, b = p0 + (int32_t)(lim < kIovSlot ? lim : kIovSlot);
+  if (lo >= hi || b <= (int32_t)lo || a >= (int32_t)hi) return 0;
+  return a >= (int32_t)lo && b <= (int32_t)hi ? 1 : 2;
+}
+
+// The bytes of the dword at packet offset x0 (-3 ..) that lie inside [lo, hi).
+YU_IOV_FN uint32_t iov_win_mask(int32_t x0, uint32_t lo, uint32_t hi) {
+  int32_t a = (int32_t)lo - x0, b = (int32_t)hi - x0;
+  a = a < 0 ? 0 : a;
+  b = b < 0 ? 0 : b;
+  const uint32_t from = a >= 4 ? 0u : ~0u << (8 * a);
+  const uint32_t upto = b >= 4 ? ~0u : ~(~0u << (8 * b));
+  return from & upto;
+}
+
+// Window byte of packet offset x in the slot whose window byte 0 is packet
+// offset p0 when the slot stores it (-1: it does not): x lies in the slot's
+// share of its view and fits the room. The same answer in every lane.
+YU_IOV_FN int32_t iov_pack_dg_held(const IovPackPlan &P, uint32_t info, int32_t p0, uint32_t x, uint32_t L) {
+  const int32_t q = (int32_t)x - p0;
+  const int32_t s = (int32_t)((info >> kIovShShift) & 3u);
+  const bool in = (info & kIovFirst) && q >= s && q - (int32_t)(16u * L) < P.hi;
+  return in ? q : -1;
+}
+
+// iov_pack_lane with four held-back positions.
+YU_IOV_FN uint32_t iov_pack_mask4(const IovPackPlan &P, uint32_t j, uint32_t L, int32_t fq0, int32_t fq1,
+                                  int32_t fq2, int32_t fq3) {
+  uint32_t m = iov_pack_mask(P, j);
+  m = iov_pack_field_clear(P, iov_pack_field_clear(P, m, j, fq0, L), j, fq1, L);
+  return iov_pack_field_clear(P, iov_pack_field_clear(P, m, j, fq2, L), j, fq3, L);
+}
+template <typename St>
+YU_IOV_FN void iov_pack_lane4(St &st, const IovPackPlan &P, uint32_t L, uint32_t cx, uint32_t cy, uint32_t cz,
+                              uint32_t cw, uint32_t prev, int32_t fq0, int32_t fq1, int32_t fq2, int32_t fq3) {
+  const uint32_t v0 = iov_pack_shift(cx, prev, P.delta), v1 = iov_pack_shift(cy, cx, P.delta);
+  const uint32_t v2 = iov_pack_shift(cz, cy, P.delta), v3 = iov_pack_shift(cw, cz, P.delta);
+  const uint64_t a = P.pa & ~3ull;
+  const uint32_t m0 = iov_pack_mask4(P, 0, L, fq0, fq1, fq2, fq3), m1 = iov_pack_mask4(P, 1, L, fq0, fq1, fq2, fq3);
+  const uint32_t m2 = iov_pack_mask4(P, 2, L, fq0, fq1, fq2, fq3), m3 = iov_pack_mask4(P, 3, L, fq0, fq1, fq2, fq3);
+  if ((m0 & m1 & m2 & m3) == 0xFu) {
+    st.b128(a, v0, v1, v2, v3);
+  } else {
+    if (m0) iov_pack_store(st, a, v0, m0);
+    if (m1) iov_pack_store(st, a + 4u, v1, m1);
+    if (m2) iov_pack_store(st, a + 8u, v2, m2);
+    if (m3) iov_pack_store(st, a + 12u, v3, m3);
+  }
+  if (P.tail && P.delta) {  // the slot's last delta bytes: window bytes past 1020, no held-back byte
+    const uint32_t mt = iov_pack_mask(P, 4);
+    if (mt) iov_pack_store(st, a + 16u, iov_pack_shift(0u, cw, P.delta), mt);
+  }
+}
+
+// Where the held-back byte at packet offset x goes when the packet is done: it
+// was held back in its slot exactly when the packet has it and the room takes
+// it (0: neither stored there nor here).
+YU_IOV_FN uint64_t iov_pack_dg_at(const IovPackDst &D, uint32_t len, uint32_t x) {
+  return x < len && x < D.room ? D.d + x : 0ull;
+}
+
+// The held-back bytes of a finished packet, stored once (the lead lane). put0 /
+// put1: the packet is in contract and the fill form stores bytes 10..11 / the
+// transport field (r0 / r1, big-endian); else the bytes as read go back: b10,
+// b11 from the gather, fb0, fb1 from the slot that held them. f: the transport
+// field's packet offset (0: none was held back).
+template <typename St>
+YU_IOV_FN void iov_pack_dg_finish(St &st, const IovPackDst &D, uint32_t len, uint32_t f, bool put0, bool put1,
+                                  uint32_t r0, uint32_t r1, uint32_t b10, uint32_t b11, uint32_t fb0,
+                                  uint32_t fb1) {
+  iov_pack_field_store(st, iov_pack_dg_at(D, len, 10u), iov_pack_dg_at(D, len, 11u), put0 ? r0 >> 8 : b10,
+                       put0 ? r0 & 0xFFu : b11);
+  if (f)
+    iov_pack_field_store(st, iov_pack_dg_at(D, len, f), iov_pack_dg_at(D, len, f + 1u), put1 ? r1 >> 8 : fb0,
+                         put1 ? r1 & 0xFFu : fb1);
+}
+
 }  // namespace yu
 #pragma GCC visibility pop
 

@@ -79,6 +79,10 @@
 //     yu_csum_pack_fill_iov, planned by yu::plan_iov_pack): k_iov's walk and sums,
 //     and every byte stored once at its place in one contiguous buffer
 //     (yucsum_iov_pack.h).
+//   k_pack_dg<U, NT, FILL>: the same for whole IPv4 datagrams
+//     (yu_csum_pack_iov_datagram / yu_csum_pack_fill_iov_datagram): k_iov's header
+//     gather, parse and epilogue, k_pack's store side over the plain walk, the window
+//     [HL, TL) applied to the sum alone.
 //   All are grid-stride kernels; the grid is sized per CU and over-subscribed
 //   (see blocks_per_cu in yucsum_plan.cpp), except that k_seg narrows it for
 //   small packets (seg_waves).
@@ -2871,6 +2875,325 @@ __global__ __launch_bounds__(256) void k_pack(const yu_iovec *views_, const uint
 }
 
 // ---------------------------------------------------------------------
+// k_pack_dg<U, NT, FILL>: whole IPv4 datagrams held as scatter-gather packets,
+// verified or filled and packed in one pass (yu_csum_pack_iov_datagram /
+// yu_csum_pack_fill_iov_datagram; named k_pack<4,dg> / k_pack<4,dg,fill>), one
+// wave per packet. A kernel of its own, so k_iov and k_pack compile as they
+// did. The store side, the tables' prefetch and the step are k_pack's; the
+// header gather, the parse and the epilogue are k_iov's datagram kind. Where
+// the two part (yucsum_iov_pack.h, last section): the walk is the plain one,
+// since the copy wants every byte, and the window [HL, TL) is applied to the
+// sum by each slot's place in the packet. FILL holds back bytes 10, 11 and the
+// transport field's two bytes from the copy and stores them when the packet is
+// done, because TL <= len is known only then: the value, or the byte as read.
+// The plain form holds nothing back and copies all bytes as they come.
+// Look-ahead: records one packet ahead (k_pack's depth; k_iov's datagram kind
+// keeps two, which here would cost a third set of record registers), the
+// header bytes of the next packet are loaded when the current one starts (its
+// records came a packet ago), and a packet is parsed as its first step begins,
+// a whole packet after its header bytes set off.
+// ---------------------------------------------------------------------
+struct PackDgPkt {
+  uint64_t g0;
+  uint32_t nv;
+  uint32_t blo, bhi, len;
+  uint64_t o0, o1;
+  uint32_t have, hb;  // lane j < have holds packet byte j; have = min(len, yu::kIovHdr)
+};
+
+struct PackDgFin {
+  bool last;
+  uint32_t len;  // bit 31: out of contract
+  uint32_t b10;  // lead lane: packet bytes 10 and 11 as read (byte 11 << 8)
+};
+
+template <int U, int NT, bool FILL>
+__global__ __launch_bounds__(256) void k_pack_dg(const yu_iovec *views_, const uint64_t *first_, PackArgs A_) {
+  PackArgs A = A_;
+  A.out = in_vgpr(A_.out);
+  A.dst = in_vgpr(A_.dst);
+  A.dst_offsets = in_vgpr(A_.dst_offsets);
+  const YU_CONST_AS yu_iovec *views = const_as(views_);
+  const YU_CONST_AS uint64_t *first = const_as(first_);
+  const uint32_t lane = threadIdx.x & 63u;
+  const bool lead = lane == 63;
+  const uint64_t wave = grid_wave(0u);
+  const uint64_t nwave = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  const int mode = A.mode;
+  if (wave >= A.n) return;
+  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+  auto dst_off = [&](uint64_t q) __attribute__((always_inline)) -> uint64_t {
+    const uint64_t ob = uniform64((uint64_t)(uintptr_t)(A.dst_offsets + (q <= A.n ? q : 0)));
+    const __amdgpu_buffer_rsrc_t ro =
+        __builtin_amdgcn_make_buffer_rsrc((void *)ob, (short)0, q <= A.n ? 8 : 0, 0x00020000);
+    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(ro, 0, 0, 0);
+    return ((uint64_t)v.y << 32) | v.x;
+  };
+  const uint64_t doN = dst_off(A.n);
+
+  struct Ahead {
+    uint64_t f0, f1;
+  };
+  auto first_pair = [&](uint64_t q, Ahead &h) __attribute__((always_inline)) {
+    h.f0 = h.f1 = 0;
+    if (q < A.n) {
+      h.f0 = first[q];
+      h.f1 = first[q + 1];
+    }
+  };
+  auto packet = [&](PackDgPkt &P, uint64_t q, const Ahead &h) __attribute__((always_inline)) {
+    const uint64_t nv = h.f1 >= h.f0 ? h.f1 - h.f0 : 0;
+    P.g0 = h.f0;
+    P.nv = nv < 0xFFFFFFFFull ? (uint32_t)nv : 0xFFFFFFFFu;
+    P.o0 = dst_off(q < A.n ? q : A.n + 1);
+    P.o1 = dst_off(q < A.n ? q + 1 : A.n + 1);
+    const uint64_t base = uniform64((uint64_t)(uintptr_t)(views_ + h.f0));
+    const __amdgpu_buffer_rsrc_t r = rsrc_at(base, base + 16u * (P.nv < 64u ? P.nv : 64u));
+    const uint4 v = bld16(r, 16u * lane, false);
+    P.blo = v.x;
+    P.bhi = v.y;
+    P.len = v.w ? 0xFFFFFFFFu : v.z;
+    P.have = P.hb = 0u;
+  };
+  // The header gather of packet P, whose records have arrived (k_iov's): lane j
+  // loads packet byte j, lanes past the packet's bytes its byte 0 again.
+  auto gather = [&](PackDgPkt &P) __attribute__((always_inline)) {
+    uint32_t off = 0, k = 0;
+    uint64_t ga = 0, a0 = 0;
+    while (off < yu::kIovHdr && k < P.nv) {
+      uint64_t b;
+      uint32_t l;
+      if (k < 64u) {
+        b = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)P.bhi, (int)k) << 32) |
+            (uint32_t)__builtin_amdgcn_readlane((int)P.blo, (int)k);
+        l = (uint32_t)__builtin_amdgcn_readlane((int)P.len, (int)k);
+      } else {
+        const uint64_t vl = views[P.g0 + k].len;
+        b = (uint64_t)(uintptr_t)views[P.g0 + k].base;
+        l = vl < 0xFFFFFFFFull ? (uint32_t)vl : 0xFFFFFFFFu;
+      }
+      l = l < 0x10000u ? l : 0x10000u;
+      if (off == 0u) a0 = b;
+      if (lane - off < l) ga = b + (lane - off);
+      off += l;
+      ++k;
+    }
+    const uint32_t have = off < yu::kIovHdr ? off : yu::kIovHdr;
+    P.have = have;
+    ga = lane < have ? ga : a0;
+    P.hb = 0u;
+    if (have) P.hb = *(const __attribute__((address_space(1))) uint8_t *)(uintptr_t)ga;
+  };
+  auto dst_of = [&](const PackDgPkt &P) __attribute__((always_inline)) -> yu::IovPackDst {
+    return {(uint64_t)(uintptr_t)A.dst + P.o0, yu::iov_pack_room(P.o0, P.o1, doN)};
+  };
+
+  uint64_t wp = wave;
+  Ahead ff;
+  PackDgPkt cur, nx;
+  {
+    Ahead a, b;
+    first_pair(wp, a);
+    first_pair(wp + nwave, b);
+    first_pair(wp + 2 * nwave, ff);
+    packet(cur, wp, a);
+    packet(nx, wp + nwave, b);
+    gather(cur);
+  }
+  yu::IovWalk W;
+  yu::iov_walk_reset(W);
+  uint32_t vi = 0;
+  int32_t vpk = 0;
+  bool fresh = true;  // the walk's next step is its packet's first
+  // the current packet's parsed header (until the next one's first step) and, in
+  // the lead lane, its sums
+  yu::IovDg D = {0u, 0u, 0u, 0u, 0u};
+  uint32_t dhs = 0, dps = 0;
+  auto parse = [&]() __attribute__((always_inline)) {
+    const int hb = (int)cur.hb;
+    yu::iov_dg_parse(D, mode, cur.have, (uint32_t)__builtin_amdgcn_readlane(hb, 0),
+                     (uint32_t)__builtin_amdgcn_readlane(hb, 2), (uint32_t)__builtin_amdgcn_readlane(hb, 3),
+                     (uint32_t)__builtin_amdgcn_readlane(hb, 9));
+    dhs = group_total<64>(yu::iov_dg_hdr_term(D.meta, mode, lane, cur.hb));
+    dps = group_total<64>(yu::iov_dg_pseudo_term(lane, cur.hb));
+  };
+
+  auto next_view = [&]() __attribute__((always_inline)) {
+    while (yu::iov_walk_done(W) && vi < cur.nv) {
+      uint64_t b;
+      uint32_t l;
+      if (vi < 64u) {
+        b = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)cur.bhi, (int)vi) << 32) |
+            (uint32_t)__builtin_amdgcn_readlane((int)cur.blo, (int)vi);
+        l = (uint32_t)__builtin_amdgcn_readlane((int)cur.len, (int)vi);
+      } else {
+        const uint64_t vl = views[cur.g0 + vi].len;
+        b = (uint64_t)(uintptr_t)views[cur.g0 + vi].base;
+        l = vl < 0xFFFFFFFFull ? (uint32_t)vl : 0xFFFFFFFFu;
+      }
+      vpk = yu::iov_pack_view(b, W.off);
+      yu::iov_walk_view(W, b, l, D.f != 0u, D.f);
+      ++vi;
+    }
+  };
+  auto produce = [&](uint32_t (&info)[U], int32_t (&po)[U], yu::IovPackDst &Dd, uint4 (&c)[U], PackDgFin &fin)
+                     __attribute__((always_inline)) {
+    if (fresh) {  // cur's header bytes set off a packet ago; nx's records came with cur's last step
+      parse();
+      gather(nx);
+      fresh = false;
+    }
+    Dd = dst_of(cur);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      next_view();
+      po[u] = yu::iov_pack_po(vpk, W.w, lane);
+      yu::IovSlot S;
+      yu::iov_walk_slot(W, S);
+      info[u] = S.info;
+      const uint32_t lim = yu::iov_lim(S.info);
+      const uint64_t base = uniform64(S.base);
+      const __amdgpu_buffer_rsrc_t r = rsrc_at(base, base + lim);
+      const uint32_t cr = 16u * lane;
+      c[u] = bld16(r, cr < lim ? cr : kOOB, NT == 1 || (NT == 2 && u != 0));
+    }
+    next_view();
+    fin.last = yu::iov_walk_done(W) && vi >= cur.nv;
+    if (fin.last) {
+      const uint32_t bad = W.over | (W.off > Dd.room ? 1u : 0u);
+      fin.len = lead ? (W.off | (bad << 31)) : 0u;
+      fin.b10 = 0u;
+      if constexpr (FILL) {
+        const int hb = (int)cur.hb;
+        fin.b10 = lead ? ((uint32_t)__builtin_amdgcn_readlane(hb, 10) |
+                          ((uint32_t)__builtin_amdgcn_readlane(hb, 11) << 8))
+                       : 0u;
+      }
+      wp += nwave;
+      cur = nx;
+      packet(nx, wp + nwave, ff);
+      first_pair(wp + 2 * nwave, ff);
+      yu::iov_walk_reset(W);
+      vi = 0;
+      vpk = 0;
+      fresh = true;
+    }
+  };
+
+  const PackStore st;
+  uint64_t p = in_vgpr(wave);
+  uint32_t accA = 0, accB = 0;
+  uint32_t jA = 0, jB = 0;
+  uint32_t cprev = 0;
+  uint32_t fb0 = 0, fb1 = 0;  // the transport field's bytes as read
+  auto step = [&](uint32_t (&ic)[U], int32_t (&pc)[U], yu::IovPackDst &Dc, uint4 (&c)[U], PackDgFin &fc)
+                  __attribute__((always_inline)) -> bool {
+    produce(ic, pc, Dc, c, fc);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint32_t info = ic[u];
+      const uint32_t lim = yu::iov_lim(info);
+      if (lim == 0) continue;
+      const int32_t p0 = __builtin_amdgcn_readfirstlane(pc[u]);  // lane 0's: the slot's window byte 0
+      const int span = yu::iov_pack_dg_span(info, p0, D.lo, D.hi);
+      uint32_t t = 0;
+      if (span == 1) {
+        if (lim >= yu::kIovSlot && !(info & yu::kIovFirst)) {
+          t = sum_full<false>(c[u], 0u, 0u);
+        } else {
+          const uint32_t hm = yu::iov_head_mask(info);
+          const uint32_t cr = 16u * lane;
+          t = yu::iov_add(yu::iov_dword(c[u].x, cr, lim, hm), t);
+          t = yu::iov_add(yu::iov_dword(c[u].y, cr + 4u, lim, hm), t);
+          t = yu::iov_add(yu::iov_dword(c[u].z, cr + 8u, lim, hm), t);
+          t = yu::iov_add(yu::iov_dword(c[u].w, cr + 12u, lim, hm), t);
+        }
+      } else if (span == 2) {  // the slot straddles HL or TL: each dword's bytes by packet offset
+        const uint32_t hm = yu::iov_head_mask(info);
+        const uint32_t cr = 16u * lane;
+        const int32_t x = pc[u];
+        t = yu::iov_add(yu::iov_dword(c[u].x, cr, lim, hm) & yu::iov_win_mask(x, D.lo, D.hi), t);
+        t = yu::iov_add(yu::iov_dword(c[u].y, cr + 4u, lim, hm) & yu::iov_win_mask(x + 4, D.lo, D.hi), t);
+        t = yu::iov_add(yu::iov_dword(c[u].z, cr + 8u, lim, hm) & yu::iov_win_mask(x + 8, D.lo, D.hi), t);
+        t = yu::iov_add(yu::iov_dword(c[u].w, cr + 12u, lim, hm) & yu::iov_win_mask(x + 12, D.lo, D.hi), t);
+      }
+      const bool swap = (info & yu::kIovSwap) != 0;
+      yu::IovPackPlan P;
+      yu::iov_pack_plan(P, info, Dc, pc[u], lane);
+      int32_t fq0 = -1, fq1 = -1;
+      if (info & (yu::kIovF0 | yu::kIovF1)) {  // TX_DATAGRAM: the transport field, inside the window
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          if (yu::iov_has_field(info, k)) {
+            const uint32_t q = yu::iov_field_q7(info, k);
+            const uint32_t word = (uint32_t)__builtin_amdgcn_readlane(
+                (int)pick_dword(c[u], (q >> 2) & 3u), (int)(q >> 4));
+            const uint32_t term = yu::iov_field_term(word, q);
+            jA += (lead && swap) ? term : 0u;
+            jB += (lead && !swap) ? term : 0u;
+            if constexpr (FILL) {
+              const bool held = yu::iov_pack_field_held(P, q, lane);
+              const uint32_t byte = (word >> (8u * (q & 3u))) & 0xFFu;
+              if (k == 0) {
+                fq0 = held ? (int32_t)q : -1;
+                fb0 = byte;
+              } else {
+                fq1 = held ? (int32_t)q : -1;
+                fb1 = byte;
+              }
+            }
+          }
+        }
+      }
+      const uint32_t prev = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(4u * ((lane - 1u) & 63u)),
+                                                                   (int)(lead ? cprev : c[u].w));
+      if (FILL && (info & yu::kIovFirst) && p0 <= 11) {  // the view's first slot reaches bytes 10, 11 (wave-uniform)
+        const int32_t fq2 = yu::iov_pack_dg_held(P, info, p0, 10u, lane);
+        const int32_t fq3 = yu::iov_pack_dg_held(P, info, p0, 11u, lane);
+        yu::iov_pack_lane4(st, P, lane, c[u].x, c[u].y, c[u].z, c[u].w, prev, fq0, fq1, fq2, fq3);
+      } else {
+        yu::iov_pack_lane(st, P, lane, c[u].x, c[u].y, c[u].z, c[u].w, prev, fq0, fq1);
+      }
+      cprev = c[u].w;
+      accA += swap ? t : 0u;
+      accB += swap ? 0u : t;
+    }
+    if (!fc.last) return true;
+    const uint32_t sA = group_total<64>(accA), sB = group_total<64>(accB);
+    if (lead) {
+      const uint32_t len = fc.len & 0x7FFFFFFFu;
+      uint32_t r0, r1;
+      bool st0, st1;
+      yu::iov_dg_value(D, mode, len, dhs, dps, sA - jA, sB - jB, r0, r1, st0, st1);
+      if (A.out) {
+        if (mode == YU_MODE_TX_DATAGRAM) {
+          A.out[2 * p] = (uint16_t)r0;
+          A.out[2 * p + 1] = (uint16_t)r1;
+        } else {
+          A.out[p] = (uint16_t)r0;
+        }
+      }
+      if constexpr (FILL) {  // binary.BigEndian.PutUint16 into the copy, or the bytes as read
+        const bool ok = !(fc.len >> 31);
+        yu::iov_pack_dg_finish(st, Dc, len, D.f, ok && st0, ok && st1, r0, r1, fc.b10 & 0xFFu, fc.b10 >> 8, fb0,
+                               fb1);
+      }
+    }
+    accA = accB = jA = jB = 0;
+    p += nwave;
+    return uniform64(p) < A.n;
+  };
+
+  uint32_t i0[U];
+  int32_t p0[U];
+  yu::IovPackDst d0;
+  uint4 c0[U];
+  PackDgFin n0;
+  while (step(i0, p0, d0, c0, n0)) {
+  }
+}
+
+// ---------------------------------------------------------------------
 // Host side: launch. Which kernel, form, load policy and grid a batch gets is
 // yu::plan's decision (yucsum_plan.cpp); here are the functions it names.
 // ---------------------------------------------------------------------
@@ -3097,9 +3420,14 @@ int batch_iov_datagram(const yu_iovec *views, const uint64_t *first_iov, uint64_
 
 // The packing form: the same tables, the packed copy besides (dst, dst_offsets).
 typedef void (*PackFn)(const yu_iovec *, const uint64_t *, const uint16_t *, const uint8_t *, PackArgs);
-const PackFn kPackFns[yu::kIovPackKernelCount][3] = {
+const PackFn kPackFns[yu::k_pack4_dg - yu::k_pack4][3] = {
     {k_pack<4, 0, false>, k_pack<4, 1, false>, k_pack<4, 2, false>},
     {k_pack<4, 0, true>, k_pack<4, 1, true>, k_pack<4, 2, true>},
+};
+typedef void (*PackDgFn)(const yu_iovec *, const uint64_t *, PackArgs);
+const PackDgFn kPackDgFns[yu::kIovPackEnd - yu::k_pack4_dg][3] = {
+    {k_pack_dg<4, 0, false>, k_pack_dg<4, 1, false>, k_pack_dg<4, 2, false>},
+    {k_pack_dg<4, 0, true>, k_pack_dg<4, 1, true>, k_pack_dg<4, 2, true>},
 };
 
 int pack_iov(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode,
@@ -3129,6 +3457,35 @@ int pack_iov(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int m
   a.mode = mode;
   hipLaunchKernelGGL(kPackFns[p.kernel - yu::k_pack4][p.policy], dim3(p.blocks), dim3(256), 0,
                      (hipStream_t)stream, views, first_iov, initial_arr, addrs, a);
+  return hip_status(hipGetLastError());
+}
+
+// The packing form for whole IPv4 datagrams: the modes that parse headers out of
+// the packet, no side arrays.
+int pack_iov_datagram(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode, uint8_t *dst,
+                      const uint64_t *dst_offsets, uint16_t *out, bool fill, void *stream) {
+  if (mode < 0 || mode >= YU_MODE_COUNT) return YU_EINVAL;      // EINVAL:mode
+  if (!yu::iov_dg_mode_ok(mode)) return YU_EINVAL;               // EINVAL:mode (a whole-packet sum: yu_csum_pack_iov takes it)
+  if (fill && !yu::iov_dg_mode_tx(mode)) return YU_EINVAL;       // EINVAL:fill-mode (VERIFY_IPV4, VERIFY_RX store no field)
+  if (!out && !fill && n) return YU_EINVAL;                      // EINVAL:out
+  if (out && !aligned(out, 2)) return YU_EINVAL;                 // EINVAL:side-align
+  if (n == 0) return YU_OK;
+  if (!first_iov || !aligned(first_iov, 8) || !aligned(views, 8)) return YU_EINVAL;  // EINVAL:offsets
+  if (!dst_offsets || !aligned(dst_offsets, 8)) return YU_EINVAL;                   // EINVAL:offsets
+  if (!views || !dst) return YU_EINVAL;                                             // EINVAL:data
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return hip_status(e);
+  const yu::IovPlan p = yu::plan_iov_pack(n, mode, fill, cu_count(dev), yu::env_knobs());
+  PackArgs a;
+  a.out = out;
+  a.dst = dst;
+  a.dst_offsets = dst_offsets;
+  a.n = n;
+  a.initial = 0;
+  a.mode = mode;
+  hipLaunchKernelGGL(kPackDgFns[p.kernel - yu::k_pack4_dg][p.policy], dim3(p.blocks), dim3(256), 0,
+                     (hipStream_t)stream, views, first_iov, a);
   return hip_status(hipGetLastError());
 }
 
@@ -3235,6 +3592,22 @@ int yu_csum_pack_fill_iov(const yu_iovec *views, const uint64_t *first_iov, uint
 const char *yu_iov_pack_variant_n(int mode, uint64_t n, int fill) {
   if (mode < 0 || mode >= YU_MODE_COUNT || !yu::iov_mode_ok(mode)) return "";
   if (fill && !yu::iov_mode_tx(mode)) return "";
+  return yu::plan_iov_pack(n, mode, fill != 0, 256, yu::env_knobs()).name;
+}
+
+int yu_csum_pack_iov_datagram(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode,
+                              uint8_t *dst, const uint64_t *dst_offsets, uint16_t *out, void *stream) {
+  return pack_iov_datagram(views, first_iov, n, mode, dst, dst_offsets, out, false, stream);
+}
+
+int yu_csum_pack_fill_iov_datagram(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode,
+                                   uint8_t *dst, const uint64_t *dst_offsets, uint16_t *out, void *stream) {
+  return pack_iov_datagram(views, first_iov, n, mode, dst, dst_offsets, out, true, stream);
+}
+
+const char *yu_iov_pack_datagram_variant_n(int mode, uint64_t n, int fill) {
+  if (mode < 0 || mode >= YU_MODE_COUNT || !yu::iov_dg_mode_ok(mode)) return "";
+  if (fill && !yu::iov_dg_mode_tx(mode)) return "";
   return yu::plan_iov_pack(n, mode, fill != 0, 256, yu::env_knobs()).name;
 }
 

@@ -308,11 +308,16 @@ IovPlan plan_iov(uint64_t n, int mode, bool fill, int cus, const Knobs &k) {
 }
 
 // k_pack: k_iov's grid and load policy (the source side is k_iov's), its own
-// kernels and names.
+// kernels and names; the whole-datagram modes get k_pack's datagram kernels.
 IovPlan plan_iov_pack(uint64_t n, int mode, bool fill, int cus, const Knobs &k) {
   IovPlan p = plan_iov(n, mode, fill, cus, k);
-  p.kernel = fill ? k_pack4_fill : k_pack4;
-  p.name = fill ? "k_pack<4,fill>" : "k_pack<4>";
+  if (p.kernel == k_iov4_dg || p.kernel == k_iov4_dg_fill) {
+    p.kernel = fill ? k_pack4_dg_fill : k_pack4_dg;
+    p.name = fill ? "k_pack<4,dg,fill>" : "k_pack<4,dg>";
+  } else {
+    p.kernel = fill ? k_pack4_fill : k_pack4;
+    p.name = fill ? "k_pack<4,fill>" : "k_pack<4>";
+  }
   return p;
 }
 

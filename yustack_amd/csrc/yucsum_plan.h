@@ -179,7 +179,9 @@ Plan plan(const Shape &s, int cus, const Knobs &k);
 enum IovKernel : uint8_t {
   k_iov4, k_iov4_fill, k_iov4_dg, k_iov4_dg_fill, kIovKernelCount,
   // k_pack (yucsum_iov_pack.h), the packing calls' family: rows of its own table
-  k_pack4 = kIovKernelCount, k_pack4_fill, kIovPackEnd
+  k_pack4 = kIovKernelCount, k_pack4_fill,
+  // k_pack_dg, the packing calls for whole IPv4 datagrams (named k_pack<4,dg>)
+  k_pack4_dg, k_pack4_dg_fill, kIovPackEnd
 };
 constexpr int kIovPackKernelCount = kIovPackEnd - k_pack4;
 struct IovPlan {
@@ -192,7 +194,9 @@ struct IovPlan {
 // datagram modes of yu_csum_batch_iov_datagram (yu::iov_dg_mode_ok): the dg kernels.
 IovPlan plan_iov(uint64_t n, int mode, bool fill, int cus, const Knobs &k);
 // The packing calls (yu_csum_pack_iov / yu_csum_pack_fill_iov): k_pack on
-// plan_iov's grid and load policy. mode: one yu::iov_mode_ok takes.
+// plan_iov's grid and load policy. mode: one yu::iov_mode_ok takes, or one of the
+// whole-datagram modes (yu_csum_pack_iov_datagram / yu_csum_pack_fill_iov_datagram):
+// the dg kernels.
 IovPlan plan_iov_pack(uint64_t n, int mode, bool fill, int cus, const Knobs &k);
 
 }  // namespace yu
