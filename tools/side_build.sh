@@ -5,6 +5,8 @@
 #   <dir>     output directory, e.g. tools/old; load it with LD_LIBRARY_PATH=<dir> (tools/ab.sh)
 #   rev       sources at that git revision (default HEAD); WORK = the working tree
 #   patch.py  run on the copied kernel file, e.g. tools/seg_trace_patch.py for tools/seg_trace
+# Copies every tracked file of yustack_amd/csrc and include/ (at rev; WORK: as the working
+# tree has them), so a new source or header needs no change here.
 set -eu
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 D=$ROOT/${1:?usage: side_build.sh <dir> [rev|WORK] [patch.py]}
@@ -12,17 +14,16 @@ REV=${2:-HEAD}
 PATCH=${3:-}
 rm -rf "$D/yustack_amd" "$D/include"
 mkdir -p "$D/yustack_amd/csrc" "$D/include"
-get() {  # get <repo path> <dest>
-  if [ "$REV" = WORK ]; then cp "$ROOT/$1" "$2"; else git -C "$ROOT" show "$REV:$1" > "$2"; fi
-}
-for f in Makefile yucsum_kernels.hip yucsum_plan.cpp yucsum_plan.h yucsum_host.cpp yucsum_scalar.cpp \
-         yucsum_internal.h; do
-  get "yustack_amd/csrc/$f" "$D/yustack_amd/csrc/$f"
-done
-get include/yucsum.h "$D/include/yucsum.h"
+if [ "$REV" = WORK ]; then
+  git -C "$ROOT" ls-files yustack_amd/csrc include | while read -r f; do
+    if [ -f "$ROOT/$f" ]; then mkdir -p "$D/$(dirname "$f")" && cp "$ROOT/$f" "$D/$f"; fi
+  done
+else
+  git -C "$ROOT" archive "$REV" yustack_amd/csrc include | tar -x -C "$D"
+fi
 if [ -n "$PATCH" ]; then python3 "$PATCH" "$D/yustack_amd/csrc/yucsum_kernels.hip"; fi
-make -s -C "$D/yustack_amd/csrc" -j8
-# one copy of the library, no objects: every gpurun call ships the tree
+make -s -C "$D/yustack_amd/csrc" -j16
+# one copy of the library, no objects
 mv "$D/yustack_amd/libyucsum.so" "$D/libyucsum.so"
 rm -rf "$D/yustack_amd/csrc/build"
 echo "built $D/libyucsum.so from ${REV}${PATCH:+ + $PATCH}"

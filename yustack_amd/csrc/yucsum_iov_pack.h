@@ -4,7 +4,8 @@
 // (yucsum_iov.h, unchanged), every byte is also stored at its place in one
 // contiguous buffer, Linux's csum_and_copy over a view list.
 //
-// The source side is k_iov's: one packet, one wave; the walk cuts each view
+// The source side is the one k_iov has, through the functions the scatter-gather
+// kernels share (yucsum_kernels.hip): one packet, one wave; the walk cuts each view
 // into slots of 1 KiB whose window starts at floor4(address); lane L holds
 // window bytes [16L, 16L + 16) as four dwords. New is where those bytes go.
 //
@@ -184,7 +185,8 @@ YU_IOV_FN void iov_pack_lane(St &st, const IovPackPlan &P, uint32_t L, uint32_t 
 // ---------------------------------------------------------------------
 // Whole IPv4 datagrams, packed (yu_csum_pack_iov_datagram /
 // yu_csum_pack_fill_iov_datagram, the kernel k_pack_dg): the header gather, the
-// parse and the epilogue are the datagram kind's (yucsum_iov.h, last section),
+// parse and the epilogue are the datagram kind's (yucsum_iov.h, last section;
+// iov_dg_gather, iov_dg_header and iov_dg_out in yucsum_kernels.hip),
 // the store side is the one above. The two do not agree on which bytes they
 // want: the copy takes every byte of the packet, the sums the header (from the
 // gathered lanes) and the window [lo, hi) = [HL, TL) only. So the walk is the

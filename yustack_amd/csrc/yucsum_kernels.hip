@@ -2202,31 +2202,21 @@ __global__ __launch_bounds__(256) void k_loop_rx(BatchArgs A) {
 }
 
 // ---------------------------------------------------------------------
-// k_iov<U, NT, FILL, DG>: scatter-gather packets (yu_csum_batch_iov /
-// yu_csum_fill_iov; DG: yu_csum_batch_iov_datagram / yu_csum_fill_iov_datagram,
-// whole IPv4 datagrams whose header is parsed out of the packet, see the end
-// of this comment), one wave per packet. The arithmetic, the walk over a
-// packet's views and the load slots it cuts them into are yucsum_iov.h's; a
-// step here is U slots, so a 2-view MTU packet (header view, payload view) is
-// one step. The loads of the next step (of this packet or the next) are issued
-// before the current one is summed, and everything a packet needs besides its
-// bytes is fetched ahead of the walk: first_iov two packets ahead with scalar
-// loads, issued at one point per packet (scalar loads return out of order, so
-// using one waits for all of them); the packet's first 64 view records, one
-// per lane, and its side data, by the lead lane, one packet ahead, with loads
-// whose idle lanes pass kOOB. The walk reads a record with v_readlane; only
-// views past a packet's 64th are read as the walk reaches them. first_iov and
-// those late records go through constant-address-space pointers, which is what
-// makes a uniform load a scalar one whatever the kernel stores: no store of a
-// call (out, the fields) may touch the tables.
+// The scatter-gather kernels (k_iov, k_pack, k_pack_dg below), one wave per
+// packet, and the parts they share. The arithmetic, the walk over a packet's
+// views and the load slots it cuts them into are yucsum_iov.h's; a step is U
+// slots, so a 2-view MTU packet (header view, payload view) is one step.
+// Everything a packet needs besides its bytes is fetched ahead of the walk:
+// first_iov with scalar loads, issued at one point per packet (scalar loads
+// return out of order, so using one waits for all of them); the packet's first
+// 64 view records, one per lane, and its side data, by the lead lane, with
+// loads whose idle lanes pass kOOB. The walk reads a record with v_readlane;
+// only views past a packet's 64th are read as the walk reaches them. first_iov
+// and those late records go through constant-address-space pointers, which is
+// what makes a uniform load a scalar one whatever the kernel stores: no store
+// of a call (out, the fields, the packed copy) may touch the tables.
 // NT: 0 plain loads, 1 nt, 2 plain for a step's first slot (a short header
 // view, whose line its neighbours share) and nt for the rest.
-// DG (IPV4, VERIFY_IPV4, VERIFY_RX, TX_DATAGRAM): lane j < 60 also loads packet
-// byte j, a packet ahead of the walk, so the records run two packets ahead and
-// first_iov three. When the walk reaches the packet its header is parsed from
-// those lanes, the header and pseudo-header sums are taken over them, and the
-// walk gets the window [HL, TL) and the packet's own field offset (yucsum_iov.h).
-// The header-only modes get an empty window: their walk only counts the bytes.
 // ---------------------------------------------------------------------
 #define YU_CONST_AS __attribute__((address_space(4)))
 template <typename T>
@@ -2234,6 +2224,182 @@ __device__ __forceinline__ const YU_CONST_AS T *const_as(const T *p) {
   return (const YU_CONST_AS T *)(uintptr_t)p;
 }
 
+// A packet's place in the view table and its first 64 view records, one per
+// lane (lanes past the packet's views hold an empty view).
+struct IovRecs {
+  uint64_t g0;      // index of the packet's first view
+  uint32_t nv;      // its views (0 when first_iov decreases: out of contract)
+  uint32_t blo, bhi, len;  // lane k: view g0 + k (a length past 32 bits is past every limit: clamped)
+};
+
+// first_iov[q], first_iov[q + 1] of packet q (none: an empty packet)
+__device__ __forceinline__ void iov_first_pair(const YU_CONST_AS uint64_t *first, uint64_t n, uint64_t q,
+                                               uint64_t &f0, uint64_t &f1) {
+  f0 = f1 = 0;
+  if (q < n) {
+    f0 = first[q];
+    f1 = first[q + 1];
+  }
+}
+
+// The packet with views [f0, f1): lane k loads record f0 + k, lanes past the
+// packet's views (and past 64 of them) nothing. (The pair by reference: see
+// k_iov's packet, which keeps its own copy of this.)
+__device__ __forceinline__ void iov_records(IovRecs &P, const yu_iovec *views, const uint64_t &f0,
+                                            const uint64_t &f1, uint32_t lane) {
+  const uint64_t nv = f1 >= f0 ? f1 - f0 : 0;
+  P.g0 = f0;
+  P.nv = nv < 0xFFFFFFFFull ? (uint32_t)nv : 0xFFFFFFFFu;
+  const uint64_t base = uniform64((uint64_t)(uintptr_t)(views + f0));
+  const __amdgpu_buffer_rsrc_t r = rsrc_at(base, base + 16u * (P.nv < 64u ? P.nv : 64u));
+  const uint4 v = bld16(r, 16u * lane, false);
+  P.blo = v.x;
+  P.bhi = v.y;
+  P.len = v.w ? 0xFFFFFFFFu : v.z;
+}
+
+// View k of packet P: a record the lanes hold, or, past the 64th, one read as it
+// is needed (a scalar load: views points into the constant address space).
+__device__ __forceinline__ void iov_record(const IovRecs &P, const YU_CONST_AS yu_iovec *views, uint32_t k,
+                                           uint64_t &b, uint32_t &l) {
+  if (k < 64u) {
+    b = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)P.bhi, (int)k) << 32) |
+        (uint32_t)__builtin_amdgcn_readlane((int)P.blo, (int)k);
+    l = (uint32_t)__builtin_amdgcn_readlane((int)P.len, (int)k);
+  } else {
+    const uint64_t vl = views[P.g0 + k].len;
+    b = (uint64_t)(uintptr_t)views[P.g0 + k].base;
+    l = vl < 0xFFFFFFFFull ? (uint32_t)vl : 0xFFFFFFFFu;
+  }
+}
+
+// A packet's side data, loaded by the lead lane alone (mine: lead lane of a
+// packet of the batch; an absent array: nothing): the {src, dst} record, and
+// initial_arr's entry or the scalar initial. Whether an array is there comes
+// apart from its pointer, which k_pack (its own copy of this, see there) keeps
+// in vector registers.
+__device__ __forceinline__ void iov_side(uint32_t &sa, uint32_t &sb, uint32_t &si, const uint8_t *addrs,
+                                         bool have_addrs, const uint16_t *initial_arr, bool have_initial,
+                                         uint32_t initial, uint64_t q, bool mine) {
+  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+  const uint32_t own = mine ? 0u : kOOB;
+  const uint64_t ab = uniform64(have_addrs ? (uint64_t)(uintptr_t)(addrs + 8 * q) : 0ull);
+  const uint64_t ib = uniform64(have_initial ? (uint64_t)(uintptr_t)(initial_arr + q) : 0ull);
+  const __amdgpu_buffer_rsrc_t ra =
+      __builtin_amdgcn_make_buffer_rsrc((void *)ab, (short)0, have_addrs ? 8 : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ri =
+      __builtin_amdgcn_make_buffer_rsrc((void *)ib, (short)0, have_initial ? 2 : 0, 0x00020000);
+  const u32x2 sab = __builtin_amdgcn_raw_buffer_load_b64(ra, (int)own, 0, 0);
+  const uint16_t sin = __builtin_amdgcn_raw_buffer_load_b16(ri, (int)own, 0, 0);
+  sa = sab.x;
+  sb = sab.y;
+  si = have_initial ? (uint32_t)sin : initial;
+}
+
+// Datagrams: the header gather of packet P, whose records have arrived. The
+// views are taken in order until they hold kIovHdr bytes (a wave-uniform loop
+// without a load but for records past the 64th); lane j takes the address of
+// packet byte j and loads it into hb. Lanes past the packet's bytes load its
+// byte 0 again, so the load is unconditional for the lanes and touches nothing
+// the packet does not hold; a packet without a byte loads nothing (a
+// wave-uniform branch). have: min(len, yu::kIovHdr). Returns the lane's address.
+__device__ __forceinline__ uint64_t iov_dg_gather(const IovRecs &P, const YU_CONST_AS yu_iovec *views,
+                                                  uint32_t lane, uint32_t &have, uint32_t &hb) {
+  uint32_t off = 0, k = 0;
+  uint64_t ga = 0, a0 = 0;
+  while (off < yu::kIovHdr && k < P.nv) {
+    uint64_t b;
+    uint32_t l;
+    iov_record(P, views, k, b, l);
+    l = l < 0x10000u ? l : 0x10000u;  // past every limit; keeps lane - off < l exact
+    if (off == 0u) a0 = b;
+    if (lane - off < l) ga = b + (lane - off);  // off <= lane < off + l
+    off += l;
+    ++k;
+  }
+  have = off < yu::kIovHdr ? off : yu::kIovHdr;
+  ga = lane < have ? ga : a0;
+  hb = 0u;
+  if (have) hb = *(const __attribute__((address_space(1))) uint8_t *)(uintptr_t)ga;
+  return ga;
+}
+
+// Datagrams: the header parsed from the gathered bytes (lane j < have holds
+// packet byte j) and, in the lead lane, the header and pseudo-header sums.
+__device__ __forceinline__ void iov_dg_header(yu::IovDg &D, uint32_t &dhs, uint32_t &dps, int mode, uint32_t have,
+                                              uint32_t hb_, uint32_t lane) {
+  const int hb = (int)hb_;
+  yu::iov_dg_parse(D, mode, have, (uint32_t)__builtin_amdgcn_readlane(hb, 0),
+                   (uint32_t)__builtin_amdgcn_readlane(hb, 2), (uint32_t)__builtin_amdgcn_readlane(hb, 3),
+                   (uint32_t)__builtin_amdgcn_readlane(hb, 9));
+  dhs = group_total<64>(yu::iov_dg_hdr_term(D.meta, mode, lane, hb_));
+  dps = group_total<64>(yu::iov_dg_pseudo_term(lane, hb_));
+}
+
+// Slot u of a step: its load, 16 bytes per lane, lanes past the slot nothing.
+template <int NT>
+__device__ __forceinline__ uint4 iov_slot_load(const yu::IovSlot &S, uint32_t lane, int u) {
+  const uint32_t lim = yu::iov_lim(S.info);
+  const uint64_t base = uniform64(S.base);
+  const __amdgpu_buffer_rsrc_t r = rsrc_at(base, base + lim);
+  const uint32_t cr = 16u * lane;
+  return bld16(r, cr < lim ? cr : kOOB, NT == 1 || (NT == 2 && u != 0));
+}
+
+// The lane's share of a slot's LE sum: a whole slot that does not begin its
+// view as it is, any other dword by dword, cut to the view's bytes.
+__device__ __forceinline__ uint32_t iov_slot_sum(const uint4 &c, uint32_t info, uint32_t lane) {
+  const uint32_t lim = yu::iov_lim(info);
+  if (lim >= yu::kIovSlot && !(info & yu::kIovFirst)) return sum_full<false>(c, 0u, 0u);
+  const uint32_t hm = yu::iov_head_mask(info);
+  const uint32_t cr = 16u * lane;
+  uint32_t t = 0;
+  t = yu::iov_add(yu::iov_dword(c.x, cr, lim, hm), t);
+  t = yu::iov_add(yu::iov_dword(c.y, cr + 4u, lim, hm), t);
+  t = yu::iov_add(yu::iov_dword(c.z, cr + 8u, lim, hm), t);
+  t = yu::iov_add(yu::iov_dword(c.w, cr + 12u, lim, hm), t);
+  return t;
+}
+
+// The field byte at slot byte q: the dword that holds it, from the lane that
+// loaded it, and the byte's term in the slot's sum.
+__device__ __forceinline__ uint32_t iov_field_byte(const uint4 &c, uint32_t q, uint32_t &word) {
+  word = (uint32_t)__builtin_amdgcn_readlane((int)pick_dword(c, (q >> 2) & 3u), (int)(q >> 4));
+  return yu::iov_field_term(word, q);
+}
+
+// A whole packet's value from its class sums, stored to out[p] (lead lane).
+__device__ __forceinline__ uint32_t iov_finish(uint16_t *out, uint64_t p, int mode, uint32_t len, uint32_t sA,
+                                               uint32_t sB, bool have_addrs, uint32_t sa, uint32_t sb, uint32_t si) {
+  const uint32_t r = yu::iov_value(mode, yu::iov_residue(sA, sB), len, have_addrs, sa, sb, si);
+  if (out) out[p] = (uint16_t)r;
+  return r;
+}
+
+// A datagram's values, stored to out (lead lane): TX_DATAGRAM has two per packet.
+__device__ __forceinline__ void iov_dg_out(uint16_t *out, uint64_t p, int mode, uint32_t r0, uint32_t r1) {
+  if (!out) return;
+  if (mode == YU_MODE_TX_DATAGRAM) {
+    out[2 * p] = (uint16_t)r0;
+    out[2 * p + 1] = (uint16_t)r1;
+  } else {
+    out[p] = (uint16_t)r0;
+  }
+}
+
+// ---------------------------------------------------------------------
+// k_iov<U, NT, FILL, DG>: scatter-gather packets (yu_csum_batch_iov /
+// yu_csum_fill_iov; DG: yu_csum_batch_iov_datagram / yu_csum_fill_iov_datagram,
+// whole IPv4 datagrams whose header is parsed out of the packet). The loads of
+// the next step (of this packet or the next) are issued before the current one
+// is summed. first_iov runs two packets ahead, the records and the side data one.
+// DG (IPV4, VERIFY_IPV4, VERIFY_RX, TX_DATAGRAM): lane j < 60 also loads packet
+// byte j, a packet ahead of the walk (iov_dg_gather), so the records run two
+// packets ahead and first_iov three. When the walk reaches the packet its
+// header is parsed and summed from those lanes (iov_dg_header), and the walk
+// gets the window [HL, TL) and the packet's own field offset (yucsum_iov.h).
+// The header-only modes get an empty window: their walk only counts the bytes.
+// ---------------------------------------------------------------------
 struct IovArgs {
   uint16_t *out;
   uint64_t n;
@@ -2241,15 +2407,10 @@ struct IovArgs {
   int mode;
 };
 
-// A packet's place in the view table and its first 64 view records, one per
-// lane (lanes past the packet's views hold an empty view).
-struct IovPkt {
-  uint64_t g0;      // index of the packet's first view
-  uint32_t nv;      // its views (0 when first_iov decreases: out of contract)
-  uint32_t blo, bhi, len;  // lane k: view g0 + k (a length past 32 bits is past every limit: clamped)
-  uint32_t sa, sb, si;     // lead lane: the {src, dst} record; initial_arr's entry or the scalar initial
+struct IovPkt : IovRecs {
+  uint32_t sa, sb, si;  // lead lane: the {src, dst} record; initial_arr's entry or the scalar initial
   // DG: lane j < have holds packet byte j, loaded from address ga
-  uint32_t have;           // min(len, yu::kIovHdr)
+  uint32_t have;
   uint32_t hb;
   uint64_t ga;
 };
@@ -2282,16 +2443,12 @@ __global__ __launch_bounds__(256) void k_iov(const yu_iovec *views_, const uint6
   const uint8_t *addrs = !DG && mode_has_pseudo(mode) ? addrs_ : nullptr;
   if (wave >= A.n) return;
 
-  // first_iov[q], first_iov[q + 1] of packet q (none: an empty packet)
-  auto first_pair = [&](uint64_t q, uint64_t &f0, uint64_t &f1) __attribute__((always_inline)) {
-    f0 = f1 = 0;
-    if (q < A.n) {
-      f0 = first[q];
-      f1 = first[q + 1];
-    }
-  };
-  // The packet with views [f0, f1): lane k loads record f0 + k, lanes past the
-  // packet's views (and past 64 of them) nothing.
+  // Packet q's records and side data (DG: no side arrays, the datagram carries
+  // its own). The record load is iov_records' text, kept here: through the
+  // function (the pair by reference, as the packing kernels compile unchanged)
+  // the fill kind's VGPRs go 85 -> 84, the datagram fill kind's 107 -> 109 and
+  // the datagram kind's SGPR spills 8 -> 6; with the pair by value k_iov keeps
+  // its lines and k_pack_dg's fill kind spills 12 SGPRs for 10.
   auto packet = [&](IovPkt &P, uint64_t q, uint64_t f0, uint64_t f1) __attribute__((always_inline)) {
     const uint64_t nv = f1 >= f0 ? f1 - f0 : 0;
     P.g0 = f0;
@@ -2305,79 +2462,31 @@ __global__ __launch_bounds__(256) void k_iov(const yu_iovec *views_, const uint6
     P.have = P.hb = 0u;
     P.ga = 0ull;
     P.sa = P.sb = P.si = 0u;
-    if constexpr (DG) return;  // no side arrays: the datagram carries its own
-    // the packet's side data, by the lead lane alone (an absent array: nothing)
-    const uint32_t own = lead && q < A.n ? 0u : kOOB;
-    const uint64_t ab = uniform64(addrs ? (uint64_t)(uintptr_t)(addrs + 8 * q) : 0ull);
-    const uint64_t ib = uniform64(initial_arr ? (uint64_t)(uintptr_t)(initial_arr + q) : 0ull);
-    const __amdgpu_buffer_rsrc_t ra =
-        __builtin_amdgcn_make_buffer_rsrc((void *)ab, (short)0, addrs ? 8 : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ri =
-        __builtin_amdgcn_make_buffer_rsrc((void *)ib, (short)0, initial_arr ? 2 : 0, 0x00020000);
-    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-    const u32x2 sab = __builtin_amdgcn_raw_buffer_load_b64(ra, (int)own, 0, 0);
-    const uint16_t sin = __builtin_amdgcn_raw_buffer_load_b16(ri, (int)own, 0, 0);
-    P.sa = sab.x;
-    P.sb = sab.y;
-    P.si = initial_arr ? (uint32_t)sin : A.initial;
+    if constexpr (!DG)
+      iov_side(P.sa, P.sb, P.si, addrs, addrs != nullptr, initial_arr, initial_arr != nullptr, A.initial, q,
+               lead && q < A.n);
   };
-
-  // View k of packet P for the gather: a record the lanes hold, or one read as it
-  // is needed (next_view's own copy of this is left as it was: through this
-  // lambda the whole-packet instantiations compile to other code).
-  auto record = [&](const IovPkt &P, uint32_t k, uint64_t &b, uint32_t &l) __attribute__((always_inline)) {
-    if (k < 64u) {
-      b = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)P.bhi, (int)k) << 32) |
-          (uint32_t)__builtin_amdgcn_readlane((int)P.blo, (int)k);
-      l = (uint32_t)__builtin_amdgcn_readlane((int)P.len, (int)k);
-    } else {  // past the records the lanes hold
-      const uint64_t vl = views[P.g0 + k].len;
-      b = (uint64_t)(uintptr_t)views[P.g0 + k].base;
-      l = vl < 0xFFFFFFFFull ? (uint32_t)vl : 0xFFFFFFFFu;
-    }
-  };
-  // DG: the header gather of packet P, whose records have arrived. The views are
-  // taken in order until they hold kIovHdr bytes (a wave-uniform loop without a
-  // load but for records past the 64th); lane j takes the address of packet byte
-  // j and loads it. Lanes past the packet's bytes load its byte 0 again, so the
-  // load is unconditional for the lanes and touches nothing the packet does not
-  // hold; a packet without a byte loads nothing (a wave-uniform branch).
   auto gather = [&](IovPkt &P) __attribute__((always_inline)) {
-    uint32_t off = 0, k = 0;
-    uint64_t ga = 0, a0 = 0;
-    while (off < yu::kIovHdr && k < P.nv) {
-      uint64_t b;
-      uint32_t l;
-      record(P, k, b, l);
-      l = l < 0x10000u ? l : 0x10000u;  // past every limit; keeps lane - off < l exact
-      if (off == 0u) a0 = b;
-      if (lane - off < l) ga = b + (lane - off);  // off <= lane < off + l
-      off += l;
-      ++k;
-    }
-    const uint32_t have = off < yu::kIovHdr ? off : yu::kIovHdr;
-    P.have = have;
-    P.ga = lane < have ? ga : a0;
-    P.hb = 0u;
-    if (have) P.hb = *(const __attribute__((address_space(1))) uint8_t *)(uintptr_t)P.ga;
+    P.ga = iov_dg_gather(P, views, lane, P.have, P.hb);
   };
 
   // The walk: packet wp, view vi of it; nx: packet wp + nwave; (ff0, ff1):
   // first_iov of packet wp + 2 nwave. DG: nx's header bytes are on their way too,
   // so the records run two packets ahead (nn: packet wp + 2 nwave) and first_iov
   // three.
-  uint64_t wp = wave, ff0, ff1;
+  uint64_t wp = wave;
+  uint64_t ff0, ff1;
   IovPkt cur, nx, nn;
   {
     uint64_t a0, a1, b0, b1;
-    first_pair(wp, a0, a1);
-    first_pair(wp + nwave, b0, b1);
-    first_pair(wp + 2 * nwave, ff0, ff1);
+    iov_first_pair(first, A.n, wp, a0, a1);
+    iov_first_pair(first, A.n, wp + nwave, b0, b1);
+    iov_first_pair(first, A.n, wp + 2 * nwave, ff0, ff1);
     packet(cur, wp, a0, a1);
     packet(nx, wp + nwave, b0, b1);
     if constexpr (DG) {
       packet(nn, wp + 2 * nwave, ff0, ff1);
-      first_pair(wp + 3 * nwave, ff0, ff1);
+      iov_first_pair(first, A.n, wp + 3 * nwave, ff0, ff1);
       gather(cur);
       gather(nx);
     }
@@ -2388,13 +2497,10 @@ __global__ __launch_bounds__(256) void k_iov(const yu_iovec *views_, const uint6
   // DG: the current packet's parsed header and, in the lead lane, its sums
   yu::IovDg D = {0u, 0u, 0u, 0u, 0u};
   uint32_t dhs = 0, dps = 0;
+  // (A lambda round the call: called at its two sites directly, the datagram
+  // kind's VGPRs go 80 -> 77, SGPR spills 8 -> 6, the datagram fill kind's 107 -> 108.)
   auto parse = [&]() __attribute__((always_inline)) {
-    const int hb = (int)cur.hb;
-    yu::iov_dg_parse(D, mode, cur.have, (uint32_t)__builtin_amdgcn_readlane(hb, 0),
-                     (uint32_t)__builtin_amdgcn_readlane(hb, 2), (uint32_t)__builtin_amdgcn_readlane(hb, 3),
-                     (uint32_t)__builtin_amdgcn_readlane(hb, 9));
-    dhs = group_total<64>(yu::iov_dg_hdr_term(D.meta, mode, lane, cur.hb));
-    dps = group_total<64>(yu::iov_dg_pseudo_term(lane, cur.hb));
+    iov_dg_header(D, dhs, dps, mode, cur.have, cur.hb, lane);
   };
   if constexpr (DG) parse();
 
@@ -2403,15 +2509,7 @@ __global__ __launch_bounds__(256) void k_iov(const yu_iovec *views_, const uint6
     while (yu::iov_walk_done(W) && vi < cur.nv) {
       uint64_t b;
       uint32_t l;
-      if (vi < 64u) {
-        b = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)cur.bhi, (int)vi) << 32) |
-            (uint32_t)__builtin_amdgcn_readlane((int)cur.blo, (int)vi);
-        l = (uint32_t)__builtin_amdgcn_readlane((int)cur.len, (int)vi);
-      } else {  // past the records the lanes hold: read as the walk gets there
-        const uint64_t vl = views[cur.g0 + vi].len;
-        b = (uint64_t)(uintptr_t)views[cur.g0 + vi].base;
-        l = vl < 0xFFFFFFFFull ? (uint32_t)vl : 0xFFFFFFFFu;
-      }
+      iov_record(cur, views, vi, b, l);
       if constexpr (DG) {
         yu::iov_walk_view_win(W, b, l, D.lo, D.hi, D.f != 0u, D.f);
       } else {
@@ -2430,11 +2528,7 @@ __global__ __launch_bounds__(256) void k_iov(const yu_iovec *views_, const uint6
       yu::IovSlot S;
       yu::iov_walk_slot(W, S);
       info[u] = S.info;
-      const uint32_t lim = yu::iov_lim(S.info);
-      const uint64_t base = uniform64(S.base);
-      const __amdgpu_buffer_rsrc_t r = rsrc_at(base, base + lim);
-      const uint32_t cr = 16u * lane;
-      c[u] = bld16(r, cr < lim ? cr : kOOB, NT == 1 || (NT == 2 && u != 0));
+      c[u] = iov_slot_load<NT>(S, lane, u);
     }
     next_view();
     fin.last = yu::iov_walk_done(W) && vi >= cur.nv;
@@ -2460,11 +2554,11 @@ __global__ __launch_bounds__(256) void k_iov(const yu_iovec *views_, const uint6
         nx = nn;
         gather(nx);
         packet(nn, wp + 2 * nwave, ff0, ff1);
-        first_pair(wp + 3 * nwave, ff0, ff1);
+        iov_first_pair(first, A.n, wp + 3 * nwave, ff0, ff1);
         parse();
       } else {
         packet(nx, wp + nwave, ff0, ff1);
-        first_pair(wp + 2 * nwave, ff0, ff1);
+        iov_first_pair(first, A.n, wp + 2 * nwave, ff0, ff1);
       }
       yu::iov_walk_reset(W);
       vi = 0;
@@ -2485,26 +2579,14 @@ __global__ __launch_bounds__(256) void k_iov(const yu_iovec *views_, const uint6
       const uint32_t info = ic[u];
       const uint32_t lim = yu::iov_lim(info);
       if (lim == 0) continue;  // an empty slot (wave-uniform): zeros came back
-      uint32_t t = 0;
-      if (lim >= yu::kIovSlot && !(info & yu::kIovFirst)) {
-        t = sum_full<false>(c[u], 0u, 0u);
-      } else {
-        const uint32_t hm = yu::iov_head_mask(info);
-        const uint32_t cr = 16u * lane;
-        t = yu::iov_add(yu::iov_dword(c[u].x, cr, lim, hm), t);
-        t = yu::iov_add(yu::iov_dword(c[u].y, cr + 4u, lim, hm), t);
-        t = yu::iov_add(yu::iov_dword(c[u].z, cr + 8u, lim, hm), t);
-        t = yu::iov_add(yu::iov_dword(c[u].w, cr + 12u, lim, hm), t);
-      }
+      const uint32_t t = iov_slot_sum(c[u], info, lane);
       const bool swap = (info & yu::kIovSwap) != 0;
       if (info & (yu::kIovF0 | yu::kIovF1)) {
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
           if (yu::iov_has_field(info, k)) {
-            const uint32_t q = yu::iov_field_q(info, k);
-            const uint32_t word = (uint32_t)__builtin_amdgcn_readlane(
-                (int)pick_dword(c[u], (q >> 2) & 3u), (int)(q >> 4));
-            const uint32_t term = yu::iov_field_term(word, q);
+            uint32_t word;
+            const uint32_t term = iov_field_byte(c[u], yu::iov_field_q(info, k), word);
             jA += (lead && swap) ? term : 0u;
             jB += (lead && !swap) ? term : 0u;
           }
@@ -2522,14 +2604,7 @@ __global__ __launch_bounds__(256) void k_iov(const yu_iovec *views_, const uint6
         uint32_t r0, r1;
         bool st0, st1;
         yu::iov_dg_value(d, mode, len, fc.hs, fc.ps, sA - jA, sB - jB, r0, r1, st0, st1);
-        if (A.out) {
-          if (mode == YU_MODE_TX_DATAGRAM) {
-            A.out[2 * p] = (uint16_t)r0;
-            A.out[2 * p + 1] = (uint16_t)r1;
-          } else {
-            A.out[p] = (uint16_t)r0;
-          }
-        }
+        iov_dg_out(A.out, p, mode, r0, r1);
         if (FILL && !(fc.len >> 31)) {  // binary.BigEndian.PutUint16 through the views
           if (st0) put_be16_at((uint8_t *)(uintptr_t)fc.ip0, (uint8_t *)(uintptr_t)fc.ip1, r0);
           if (st1) put_be16_at((uint8_t *)(uintptr_t)fc.fp0, (uint8_t *)(uintptr_t)fc.fp1, r1);
@@ -2542,18 +2617,9 @@ __global__ __launch_bounds__(256) void k_iov(const yu_iovec *views_, const uint6
         sA -= jA;
         sB -= jB;
       }
-      const uint32_t r = yu::iov_value(mode, yu::iov_residue(sA, sB), len, addrs != nullptr, fc.sa,
-                                       fc.sb, fc.si);
-      if (A.out) A.out[p] = (uint16_t)r;
-      if (FILL && fld && !(fc.len >> 31)) {  // binary.BigEndian.PutUint16 through the views
-        uint8_t *q0 = (uint8_t *)(uintptr_t)fc.fp0, *q1 = (uint8_t *)(uintptr_t)fc.fp1;
-        if (q1 == q0 + 1 && ((uintptr_t)q0 & 1u) == 0) {
-          *(uint16_t *)q0 = (uint16_t)(((r >> 8) | (r << 8)) & 0xFFFFu);
-        } else {
-          *q0 = (uint8_t)(r >> 8);
-          *q1 = (uint8_t)r;
-        }
-      }
+      const uint32_t r = iov_finish(A.out, p, mode, len, sA, sB, addrs != nullptr, fc.sa, fc.sb, fc.si);
+      if (FILL && fld && !(fc.len >> 31))  // binary.BigEndian.PutUint16 through the views
+        put_be16_at((uint8_t *)(uintptr_t)fc.fp0, (uint8_t *)(uintptr_t)fc.fp1, r);
     }
     accA = accB = jA = jB = 0;
     p += nwave;
@@ -2572,12 +2638,16 @@ __global__ __launch_bounds__(256) void k_iov(const yu_iovec *views_, const uint6
 
 // ---------------------------------------------------------------------
 // k_pack<U, NT, FILL>: scatter-gather packets summed and packed in one pass
-// (yu_csum_pack_iov / yu_csum_pack_fill_iov), one wave per packet. The walk, the
-// prefetch of first_iov, records and side data, the slots and the sums are
-// k_iov's whole-packet kind (above; yucsum_iov.h), so the value is k_iov's (a
-// step's loads are summed in the step itself, not one step later). New
-// is the store side (yucsum_iov_pack.h): as a slot is summed, its bytes are
-// shifted to the destination's dword phase (v_alignbyte with the neighbour
+// (yu_csum_pack_iov / yu_csum_pack_fill_iov). The walk, the prefetch, the slots,
+// the sums and the value are k_iov's whole-packet kind (a step's loads are
+// summed in the step itself, not one step later), here as text of its own and
+// not through the shared functions above: through them every resource-usage
+// line stayed but the code moved (17448 -> 17452 and 17504 -> 17516 bytes),
+// and pack_fused measured 0.4 % (tcp1500) and 0.7 % (udp72) slower than the
+// parent, outside the parent's own spread (profiles/r12/iov_refactor_ab_r12.log).
+// A change to a shared part must be made here too. Its own is the store side
+// (yucsum_iov_pack.h): as a slot is summed, its bytes are shifted to the
+// destination's dword phase (v_alignbyte with the neighbour
 // lane's last dword, one ds_bpermute; across a slot seam the previous slot's last
 // dword, which lane 63 kept) and stored: whole dwords four at a time, the edge
 // dwords of a view's span by 16-bit and byte stores, never a read-modify-write.
@@ -2632,6 +2702,28 @@ template <typename T>
 __device__ __forceinline__ T in_vgpr(T x) {
   asm volatile("" : "+v"(x));
   return x;
+}
+
+// dst_offsets[q] in every lane (past the table, q > n: 0)
+__device__ __forceinline__ uint64_t pack_dst_off(const uint64_t *dst_offsets, uint64_t n, uint64_t q) {
+  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+  const uint64_t ob = uniform64((uint64_t)(uintptr_t)(dst_offsets + (q <= n ? q : 0)));
+  const __amdgpu_buffer_rsrc_t ro =
+      __builtin_amdgcn_make_buffer_rsrc((void *)ob, (short)0, q <= n ? 8 : 0, 0x00020000);
+  const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(ro, 0, 0, 0);
+  return ((uint64_t)v.y << 32) | v.x;
+}
+
+// Packet q's dst_offsets pair (past the batch: zeros).
+__device__ __forceinline__ void pack_dst_pair(uint64_t &o0, uint64_t &o1, const uint64_t *dst_offsets, uint64_t n,
+                                              uint64_t q) {
+  o0 = pack_dst_off(dst_offsets, n, q < n ? q : n + 1);
+  o1 = pack_dst_off(dst_offsets, n, q < n ? q + 1 : n + 1);
+}
+
+// Where the packet with the pair (o0, o1) goes, in every lane (doN: dst_offsets[n]).
+__device__ __forceinline__ yu::IovPackDst pack_dst_of(const uint8_t *dst, uint64_t o0, uint64_t o1, uint64_t doN) {
+  return {(uint64_t)(uintptr_t)dst + o0, yu::iov_pack_room(o0, o1, doN)};
 }
 
 template <int U, int NT, bool FILL>
@@ -2877,10 +2969,11 @@ __global__ __launch_bounds__(256) void k_pack(const yu_iovec *views_, const uint
 // ---------------------------------------------------------------------
 // k_pack_dg<U, NT, FILL>: whole IPv4 datagrams held as scatter-gather packets,
 // verified or filled and packed in one pass (yu_csum_pack_iov_datagram /
-// yu_csum_pack_fill_iov_datagram; named k_pack<4,dg> / k_pack<4,dg,fill>), one
-// wave per packet. A kernel of its own, so k_iov and k_pack compile as they
-// did. The store side, the tables' prefetch and the step are k_pack's; the
-// header gather, the parse and the epilogue are k_iov's datagram kind. Where
+// yu_csum_pack_fill_iov_datagram; named k_pack<4,dg> / k_pack<4,dg,fill>). A
+// kernel of its own, so k_iov and k_pack compile as they did. The store side
+// and the step are k_pack's, the prefetch pack_dst_pair and iov_records as
+// there; the header comes by iov_dg_gather and iov_dg_header and the values
+// leave by iov_dg_out as in k_iov's datagram kind. Where
 // the two part (yucsum_iov_pack.h, last section): the walk is the plain one,
 // since the copy wants every byte, and the window [HL, TL) is applied to the
 // sum by each slot's place in the packet. FILL holds back bytes 10, 11 and the
@@ -2893,10 +2986,7 @@ __global__ __launch_bounds__(256) void k_pack(const yu_iovec *views_, const uint
 // records came a packet ago), and a packet is parsed as its first step begins,
 // a whole packet after its header bytes set off.
 // ---------------------------------------------------------------------
-struct PackDgPkt {
-  uint64_t g0;
-  uint32_t nv;
-  uint32_t blo, bhi, len;
+struct PackDgPkt : IovRecs {
   uint64_t o0, o1;
   uint32_t have, hb;  // lane j < have holds packet byte j; have = min(len, yu::kIovHdr)
 };
@@ -2921,83 +3011,27 @@ __global__ __launch_bounds__(256) void k_pack_dg(const yu_iovec *views_, const u
   const uint64_t nwave = (uint64_t)gridDim.x * (blockDim.x >> 6);
   const int mode = A.mode;
   if (wave >= A.n) return;
-  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-  auto dst_off = [&](uint64_t q) __attribute__((always_inline)) -> uint64_t {
-    const uint64_t ob = uniform64((uint64_t)(uintptr_t)(A.dst_offsets + (q <= A.n ? q : 0)));
-    const __amdgpu_buffer_rsrc_t ro =
-        __builtin_amdgcn_make_buffer_rsrc((void *)ob, (short)0, q <= A.n ? 8 : 0, 0x00020000);
-    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(ro, 0, 0, 0);
-    return ((uint64_t)v.y << 32) | v.x;
-  };
-  const uint64_t doN = dst_off(A.n);
+  const uint64_t doN = pack_dst_off(A.dst_offsets, A.n, A.n);
 
-  struct Ahead {
-    uint64_t f0, f1;
-  };
-  auto first_pair = [&](uint64_t q, Ahead &h) __attribute__((always_inline)) {
-    h.f0 = h.f1 = 0;
-    if (q < A.n) {
-      h.f0 = first[q];
-      h.f1 = first[q + 1];
-    }
-  };
-  auto packet = [&](PackDgPkt &P, uint64_t q, const Ahead &h) __attribute__((always_inline)) {
-    const uint64_t nv = h.f1 >= h.f0 ? h.f1 - h.f0 : 0;
-    P.g0 = h.f0;
-    P.nv = nv < 0xFFFFFFFFull ? (uint32_t)nv : 0xFFFFFFFFu;
-    P.o0 = dst_off(q < A.n ? q : A.n + 1);
-    P.o1 = dst_off(q < A.n ? q + 1 : A.n + 1);
-    const uint64_t base = uniform64((uint64_t)(uintptr_t)(views_ + h.f0));
-    const __amdgpu_buffer_rsrc_t r = rsrc_at(base, base + 16u * (P.nv < 64u ? P.nv : 64u));
-    const uint4 v = bld16(r, 16u * lane, false);
-    P.blo = v.x;
-    P.bhi = v.y;
-    P.len = v.w ? 0xFFFFFFFFu : v.z;
+  auto packet = [&](PackDgPkt &P, uint64_t q, uint64_t f0, uint64_t f1) __attribute__((always_inline)) {
+    pack_dst_pair(P.o0, P.o1, A.dst_offsets, A.n, q);
+    iov_records(P, views_, f0, f1, lane);
     P.have = P.hb = 0u;
   };
-  // The header gather of packet P, whose records have arrived (k_iov's): lane j
-  // loads packet byte j, lanes past the packet's bytes its byte 0 again.
-  auto gather = [&](PackDgPkt &P) __attribute__((always_inline)) {
-    uint32_t off = 0, k = 0;
-    uint64_t ga = 0, a0 = 0;
-    while (off < yu::kIovHdr && k < P.nv) {
-      uint64_t b;
-      uint32_t l;
-      if (k < 64u) {
-        b = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)P.bhi, (int)k) << 32) |
-            (uint32_t)__builtin_amdgcn_readlane((int)P.blo, (int)k);
-        l = (uint32_t)__builtin_amdgcn_readlane((int)P.len, (int)k);
-      } else {
-        const uint64_t vl = views[P.g0 + k].len;
-        b = (uint64_t)(uintptr_t)views[P.g0 + k].base;
-        l = vl < 0xFFFFFFFFull ? (uint32_t)vl : 0xFFFFFFFFu;
-      }
-      l = l < 0x10000u ? l : 0x10000u;
-      if (off == 0u) a0 = b;
-      if (lane - off < l) ga = b + (lane - off);
-      off += l;
-      ++k;
-    }
-    const uint32_t have = off < yu::kIovHdr ? off : yu::kIovHdr;
-    P.have = have;
-    ga = lane < have ? ga : a0;
-    P.hb = 0u;
-    if (have) P.hb = *(const __attribute__((address_space(1))) uint8_t *)(uintptr_t)ga;
-  };
-  auto dst_of = [&](const PackDgPkt &P) __attribute__((always_inline)) -> yu::IovPackDst {
-    return {(uint64_t)(uintptr_t)A.dst + P.o0, yu::iov_pack_room(P.o0, P.o1, doN)};
+  auto gather = [&](PackDgPkt &P) __attribute__((always_inline)) {  // bytes 10, 11 go by offset: no address kept
+    iov_dg_gather(P, views, lane, P.have, P.hb);
   };
 
   uint64_t wp = wave;
-  Ahead ff;
+  uint64_t ff0, ff1;
   PackDgPkt cur, nx;
   {
-    Ahead a, b;
-    first_pair(wp, a);
-    first_pair(wp + nwave, b);
-    first_pair(wp + 2 * nwave, ff);
-    packet(cur, wp, a);
-    packet(nx, wp + nwave, b);
+    uint64_t a0, a1, b0, b1;
+    iov_first_pair(first, A.n, wp, a0, a1);
+    iov_first_pair(first, A.n, wp + nwave, b0, b1);
+    iov_first_pair(first, A.n, wp + 2 * nwave, ff0, ff1);
+    packet(cur, wp, a0, a1);
+    packet(nx, wp + nwave, b0, b1);
     gather(cur);
   }
   yu::IovWalk W;
@@ -3009,28 +3043,12 @@ __global__ __launch_bounds__(256) void k_pack_dg(const yu_iovec *views_, const u
   // the lead lane, its sums
   yu::IovDg D = {0u, 0u, 0u, 0u, 0u};
   uint32_t dhs = 0, dps = 0;
-  auto parse = [&]() __attribute__((always_inline)) {
-    const int hb = (int)cur.hb;
-    yu::iov_dg_parse(D, mode, cur.have, (uint32_t)__builtin_amdgcn_readlane(hb, 0),
-                     (uint32_t)__builtin_amdgcn_readlane(hb, 2), (uint32_t)__builtin_amdgcn_readlane(hb, 3),
-                     (uint32_t)__builtin_amdgcn_readlane(hb, 9));
-    dhs = group_total<64>(yu::iov_dg_hdr_term(D.meta, mode, lane, cur.hb));
-    dps = group_total<64>(yu::iov_dg_pseudo_term(lane, cur.hb));
-  };
 
   auto next_view = [&]() __attribute__((always_inline)) {
     while (yu::iov_walk_done(W) && vi < cur.nv) {
       uint64_t b;
       uint32_t l;
-      if (vi < 64u) {
-        b = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)cur.bhi, (int)vi) << 32) |
-            (uint32_t)__builtin_amdgcn_readlane((int)cur.blo, (int)vi);
-        l = (uint32_t)__builtin_amdgcn_readlane((int)cur.len, (int)vi);
-      } else {
-        const uint64_t vl = views[cur.g0 + vi].len;
-        b = (uint64_t)(uintptr_t)views[cur.g0 + vi].base;
-        l = vl < 0xFFFFFFFFull ? (uint32_t)vl : 0xFFFFFFFFu;
-      }
+      iov_record(cur, views, vi, b, l);
       vpk = yu::iov_pack_view(b, W.off);
       yu::iov_walk_view(W, b, l, D.f != 0u, D.f);
       ++vi;
@@ -3039,11 +3057,11 @@ __global__ __launch_bounds__(256) void k_pack_dg(const yu_iovec *views_, const u
   auto produce = [&](uint32_t (&info)[U], int32_t (&po)[U], yu::IovPackDst &Dd, uint4 (&c)[U], PackDgFin &fin)
                      __attribute__((always_inline)) {
     if (fresh) {  // cur's header bytes set off a packet ago; nx's records came with cur's last step
-      parse();
+      iov_dg_header(D, dhs, dps, mode, cur.have, cur.hb, lane);
       gather(nx);
       fresh = false;
     }
-    Dd = dst_of(cur);
+    Dd = pack_dst_of(A.dst, cur.o0, cur.o1, doN);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       next_view();
@@ -3051,11 +3069,7 @@ __global__ __launch_bounds__(256) void k_pack_dg(const yu_iovec *views_, const u
       yu::IovSlot S;
       yu::iov_walk_slot(W, S);
       info[u] = S.info;
-      const uint32_t lim = yu::iov_lim(S.info);
-      const uint64_t base = uniform64(S.base);
-      const __amdgpu_buffer_rsrc_t r = rsrc_at(base, base + lim);
-      const uint32_t cr = 16u * lane;
-      c[u] = bld16(r, cr < lim ? cr : kOOB, NT == 1 || (NT == 2 && u != 0));
+      c[u] = iov_slot_load<NT>(S, lane, u);
     }
     next_view();
     fin.last = yu::iov_walk_done(W) && vi >= cur.nv;
@@ -3071,8 +3085,8 @@ __global__ __launch_bounds__(256) void k_pack_dg(const yu_iovec *views_, const u
       }
       wp += nwave;
       cur = nx;
-      packet(nx, wp + nwave, ff);
-      first_pair(wp + 2 * nwave, ff);
+      packet(nx, wp + nwave, ff0, ff1);
+      iov_first_pair(first, A.n, wp + 2 * nwave, ff0, ff1);
       yu::iov_walk_reset(W);
       vi = 0;
       vpk = 0;
@@ -3098,16 +3112,7 @@ __global__ __launch_bounds__(256) void k_pack_dg(const yu_iovec *views_, const u
       const int span = yu::iov_pack_dg_span(info, p0, D.lo, D.hi);
       uint32_t t = 0;
       if (span == 1) {
-        if (lim >= yu::kIovSlot && !(info & yu::kIovFirst)) {
-          t = sum_full<false>(c[u], 0u, 0u);
-        } else {
-          const uint32_t hm = yu::iov_head_mask(info);
-          const uint32_t cr = 16u * lane;
-          t = yu::iov_add(yu::iov_dword(c[u].x, cr, lim, hm), t);
-          t = yu::iov_add(yu::iov_dword(c[u].y, cr + 4u, lim, hm), t);
-          t = yu::iov_add(yu::iov_dword(c[u].z, cr + 8u, lim, hm), t);
-          t = yu::iov_add(yu::iov_dword(c[u].w, cr + 12u, lim, hm), t);
-        }
+        t = iov_slot_sum(c[u], info, lane);
       } else if (span == 2) {  // the slot straddles HL or TL: each dword's bytes by packet offset
         const uint32_t hm = yu::iov_head_mask(info);
         const uint32_t cr = 16u * lane;
@@ -3126,9 +3131,8 @@ __global__ __launch_bounds__(256) void k_pack_dg(const yu_iovec *views_, const u
         for (int k = 0; k < 2; ++k) {
           if (yu::iov_has_field(info, k)) {
             const uint32_t q = yu::iov_field_q7(info, k);
-            const uint32_t word = (uint32_t)__builtin_amdgcn_readlane(
-                (int)pick_dword(c[u], (q >> 2) & 3u), (int)(q >> 4));
-            const uint32_t term = yu::iov_field_term(word, q);
+            uint32_t word;
+            const uint32_t term = iov_field_byte(c[u], q, word);
             jA += (lead && swap) ? term : 0u;
             jB += (lead && !swap) ? term : 0u;
             if constexpr (FILL) {
@@ -3165,14 +3169,7 @@ __global__ __launch_bounds__(256) void k_pack_dg(const yu_iovec *views_, const u
       uint32_t r0, r1;
       bool st0, st1;
       yu::iov_dg_value(D, mode, len, dhs, dps, sA - jA, sB - jB, r0, r1, st0, st1);
-      if (A.out) {
-        if (mode == YU_MODE_TX_DATAGRAM) {
-          A.out[2 * p] = (uint16_t)r0;
-          A.out[2 * p + 1] = (uint16_t)r1;
-        } else {
-          A.out[p] = (uint16_t)r0;
-        }
-      }
+      iov_dg_out(A.out, p, mode, r0, r1);
       if constexpr (FILL) {  // binary.BigEndian.PutUint16 into the copy, or the bytes as read
         const bool ok = !(fc.len >> 31);
         yu::iov_pack_dg_finish(st, Dc, len, D.f, ok && st0, ok && st1, r0, r1, fc.b10 & 0xFFu, fc.b10 >> 8, fb0,
@@ -3362,62 +3359,6 @@ const IovFn kIovFns[yu::kIovKernelCount][3] = {
     {k_iov<4, 0, false, true>, k_iov<4, 1, false, true>, k_iov<4, 2, false, true>},
     {k_iov<4, 0, true, true>, k_iov<4, 1, true, true>, k_iov<4, 2, true, true>},
 };
-
-// The scatter-gather device calls. The tables are device memory and are not
-// read here (include/yucsum.h, "Out of contract").
-int batch_iov(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode,
-              const uint16_t *initial_arr, uint16_t initial, const uint8_t *addrs, uint16_t *out,
-              bool fill, void *stream) {
-  if (mode < 0 || mode >= YU_MODE_COUNT) return YU_EINVAL;     // EINVAL:mode
-  if (fill && !yu::iov_mode_tx(mode)) return YU_EINVAL;         // EINVAL:fill-mode (no field, or a mode this form refuses)
-  if (!yu::iov_mode_ok(mode)) return YU_EINVAL;                 // EINVAL:mode (IPV4, VERIFY_IPV4, VERIFY_RX, TX_DATAGRAM parse headers)
-  if (!out && !fill && n) return YU_EINVAL;                     // EINVAL:out
-  if (initial_arr && !aligned(initial_arr, 2)) return YU_EINVAL;  // EINVAL:side-align
-  if (addrs && !aligned(addrs, 4)) return YU_EINVAL;              // EINVAL:side-align
-  if (out && !aligned(out, 2)) return YU_EINVAL;                  // EINVAL:side-align
-  if (n == 0) return YU_OK;
-  if (!first_iov || !aligned(first_iov, 8) || !aligned(views, 8)) return YU_EINVAL;  // EINVAL:offsets
-  if (!views) return YU_EINVAL;                                                     // EINVAL:data
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return hip_status(e);
-  const yu::IovPlan p = yu::plan_iov(n, mode, fill, cu_count(dev), yu::env_knobs());
-  IovArgs a;
-  a.out = out;
-  a.n = n;
-  a.initial = initial;
-  a.mode = mode;
-  hipLaunchKernelGGL(kIovFns[p.kernel][p.policy], dim3(p.blocks), dim3(256), 0, (hipStream_t)stream,
-                     views, first_iov, initial_arr, addrs, a);
-  return hip_status(hipGetLastError());
-}
-
-// The same for whole IPv4 datagrams: the modes that parse headers out of the
-// packet, which take no side arrays.
-int batch_iov_datagram(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode,
-                       uint16_t *out, bool fill, void *stream) {
-  if (mode < 0 || mode >= YU_MODE_COUNT) return YU_EINVAL;      // EINVAL:mode
-  if (!yu::iov_dg_mode_ok(mode)) return YU_EINVAL;               // EINVAL:mode (a whole-packet sum: yu_csum_batch_iov takes it)
-  if (fill && !yu::iov_dg_mode_tx(mode)) return YU_EINVAL;       // EINVAL:fill-mode (VERIFY_IPV4, VERIFY_RX store no field)
-  if (!out && !fill && n) return YU_EINVAL;                      // EINVAL:out
-  if (out && !aligned(out, 2)) return YU_EINVAL;                 // EINVAL:side-align
-  if (n == 0) return YU_OK;
-  if (!first_iov || !aligned(first_iov, 8) || !aligned(views, 8)) return YU_EINVAL;  // EINVAL:offsets
-  if (!views) return YU_EINVAL;                                                     // EINVAL:data
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return hip_status(e);
-  const yu::IovPlan p = yu::plan_iov(n, mode, fill, cu_count(dev), yu::env_knobs());
-  IovArgs a;
-  a.out = out;
-  a.n = n;
-  a.initial = 0;
-  a.mode = mode;
-  hipLaunchKernelGGL(kIovFns[p.kernel][p.policy], dim3(p.blocks), dim3(256), 0, (hipStream_t)stream,
-                     views, first_iov, (const uint16_t *)nullptr, (const uint8_t *)nullptr, a);
-  return hip_status(hipGetLastError());
-}
-
 // The packing form: the same tables, the packed copy besides (dst, dst_offsets).
 typedef void (*PackFn)(const yu_iovec *, const uint64_t *, const uint16_t *, const uint8_t *, PackArgs);
 const PackFn kPackFns[yu::k_pack4_dg - yu::k_pack4][3] = {
@@ -3430,63 +3371,79 @@ const PackDgFn kPackDgFns[yu::kIovPackEnd - yu::k_pack4_dg][3] = {
     {k_pack_dg<4, 0, true>, k_pack_dg<4, 1, true>, k_pack_dg<4, 2, true>},
 };
 
-int pack_iov(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode,
-             const uint16_t *initial_arr, uint16_t initial, const uint8_t *addrs, uint8_t *dst,
-             const uint64_t *dst_offsets, uint16_t *out, bool fill, void *stream) {
-  if (mode < 0 || mode >= YU_MODE_COUNT) return YU_EINVAL;     // EINVAL:mode
-  if (fill && !yu::iov_mode_tx(mode)) return YU_EINVAL;         // EINVAL:fill-mode (no field, or a mode this form refuses)
-  if (!yu::iov_mode_ok(mode)) return YU_EINVAL;                 // EINVAL:mode (IPV4, VERIFY_IPV4, VERIFY_RX, TX_DATAGRAM parse headers)
-  if (!out && !fill && n) return YU_EINVAL;                     // EINVAL:out
-  if (initial_arr && !aligned(initial_arr, 2)) return YU_EINVAL;  // EINVAL:side-align
-  if (addrs && !aligned(addrs, 4)) return YU_EINVAL;              // EINVAL:side-align
-  if (out && !aligned(out, 2)) return YU_EINVAL;                  // EINVAL:side-align
-  if (n == 0) return YU_OK;
-  if (!first_iov || !aligned(first_iov, 8) || !aligned(views, 8)) return YU_EINVAL;  // EINVAL:offsets
-  if (!dst_offsets || !aligned(dst_offsets, 8)) return YU_EINVAL;                   // EINVAL:offsets
-  if (!views || !dst) return YU_EINVAL;                                             // EINVAL:data
+// A scatter-gather device call. dg: the form for whole IPv4 datagrams, the modes
+// that parse headers out of the packet, which takes no side arrays (initial_arr,
+// addrs: null; initial: 0). pack: the packing form, with dst and dst_offsets
+// (null otherwise).
+struct IovCall {
+  bool dg, pack;
+  const yu_iovec *views;
+  const uint64_t *first_iov;
+  uint64_t n;
+  int mode;
+  const uint16_t *initial_arr;
+  uint16_t initial;
+  const uint8_t *addrs;
+  uint8_t *dst;
+  const uint64_t *dst_offsets;
+  uint16_t *out;
+  bool fill;
+  void *stream;
+};
+
+// Its arguments. The tables are device memory and are not read here
+// (include/yucsum.h, "Out of contract"); an empty batch passes before they are
+// looked at.
+int check_iov(const IovCall &c) {
+  const int mode = c.mode;
+  if (mode < 0 || mode >= YU_MODE_COUNT) return YU_EINVAL;      // EINVAL:mode
+  if (c.dg && !yu::iov_dg_mode_ok(mode)) return YU_EINVAL;       // EINVAL:mode (a whole-packet sum: the whole-packet form takes it)
+  if (c.fill && !(c.dg ? yu::iov_dg_mode_tx(mode) : yu::iov_mode_tx(mode)))
+    return YU_EINVAL;  // EINVAL:fill-mode (no field: VERIFY_IPV4, VERIFY_RX store none; or a mode this form refuses)
+  if (!c.dg && !yu::iov_mode_ok(mode)) return YU_EINVAL;         // EINVAL:mode (IPV4, VERIFY_IPV4, VERIFY_RX, TX_DATAGRAM parse headers)
+  if (!c.out && !c.fill && c.n) return YU_EINVAL;                // EINVAL:out
+  if (c.initial_arr && !aligned(c.initial_arr, 2)) return YU_EINVAL;  // EINVAL:side-align
+  if (c.addrs && !aligned(c.addrs, 4)) return YU_EINVAL;              // EINVAL:side-align
+  if (c.out && !aligned(c.out, 2)) return YU_EINVAL;                  // EINVAL:side-align
+  if (c.n == 0) return YU_OK;
+  if (!c.first_iov || !aligned(c.first_iov, 8) || !aligned(c.views, 8)) return YU_EINVAL;  // EINVAL:offsets
+  if (c.pack && (!c.dst_offsets || !aligned(c.dst_offsets, 8))) return YU_EINVAL;         // EINVAL:offsets
+  if (!c.views || (c.pack && !c.dst)) return YU_EINVAL;                                   // EINVAL:data
+  return YU_OK;
+}
+
+// The call: checked, then the device's plan and its kernel's launch.
+int call_iov(const IovCall &c) {
+  const int rc = check_iov(c);
+  if (rc != YU_OK || c.n == 0) return rc;
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return hip_status(e);
-  const yu::IovPlan p = yu::plan_iov_pack(n, mode, fill, cu_count(dev), yu::env_knobs());
-  PackArgs a;
-  a.out = out;
-  a.dst = dst;
-  a.dst_offsets = dst_offsets;
-  a.n = n;
-  a.initial = initial;
-  a.mode = mode;
-  hipLaunchKernelGGL(kPackFns[p.kernel - yu::k_pack4][p.policy], dim3(p.blocks), dim3(256), 0,
-                     (hipStream_t)stream, views, first_iov, initial_arr, addrs, a);
+  const yu::IovPlan p = (c.pack ? yu::plan_iov_pack : yu::plan_iov)(c.n, c.mode, c.fill, cu_count(dev), yu::env_knobs());
+  const dim3 grid(p.blocks), block(256);
+  const hipStream_t stream = (hipStream_t)c.stream;
+  if (!c.pack) {
+    const IovArgs a = {c.out, c.n, c.initial, c.mode};
+    hipLaunchKernelGGL(kIovFns[p.kernel][p.policy], grid, block, 0, stream, c.views, c.first_iov, c.initial_arr,
+                       c.addrs, a);
+    return hip_status(hipGetLastError());
+  }
+  const PackArgs a = {c.out, c.dst, c.dst_offsets, c.n, c.initial, c.mode};
+  if (c.dg)
+    hipLaunchKernelGGL(kPackDgFns[p.kernel - yu::k_pack4_dg][p.policy], grid, block, 0, stream, c.views,
+                       c.first_iov, a);
+  else
+    hipLaunchKernelGGL(kPackFns[p.kernel - yu::k_pack4][p.policy], grid, block, 0, stream, c.views, c.first_iov,
+                       c.initial_arr, c.addrs, a);
   return hip_status(hipGetLastError());
 }
 
-// The packing form for whole IPv4 datagrams: the modes that parse headers out of
-// the packet, no side arrays.
-int pack_iov_datagram(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode, uint8_t *dst,
-                      const uint64_t *dst_offsets, uint16_t *out, bool fill, void *stream) {
-  if (mode < 0 || mode >= YU_MODE_COUNT) return YU_EINVAL;      // EINVAL:mode
-  if (!yu::iov_dg_mode_ok(mode)) return YU_EINVAL;               // EINVAL:mode (a whole-packet sum: yu_csum_pack_iov takes it)
-  if (fill && !yu::iov_dg_mode_tx(mode)) return YU_EINVAL;       // EINVAL:fill-mode (VERIFY_IPV4, VERIFY_RX store no field)
-  if (!out && !fill && n) return YU_EINVAL;                      // EINVAL:out
-  if (out && !aligned(out, 2)) return YU_EINVAL;                 // EINVAL:side-align
-  if (n == 0) return YU_OK;
-  if (!first_iov || !aligned(first_iov, 8) || !aligned(views, 8)) return YU_EINVAL;  // EINVAL:offsets
-  if (!dst_offsets || !aligned(dst_offsets, 8)) return YU_EINVAL;                   // EINVAL:offsets
-  if (!views || !dst) return YU_EINVAL;                                             // EINVAL:data
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return hip_status(e);
-  const yu::IovPlan p = yu::plan_iov_pack(n, mode, fill, cu_count(dev), yu::env_knobs());
-  PackArgs a;
-  a.out = out;
-  a.dst = dst;
-  a.dst_offsets = dst_offsets;
-  a.n = n;
-  a.initial = 0;
-  a.mode = mode;
-  hipLaunchKernelGGL(kPackDgFns[p.kernel - yu::k_pack4_dg][p.policy], dim3(p.blocks), dim3(256), 0,
-                     (hipStream_t)stream, views, first_iov, a);
-  return hip_status(hipGetLastError());
+// The yu_iov*_variant_n calls: "" for a mode (or a fill) the form refuses.
+const char *iov_variant(bool dg, bool pack, int mode, uint64_t n, int fill) {
+  if (mode < 0 || mode >= YU_MODE_COUNT) return "";
+  if (!(dg ? yu::iov_dg_mode_ok(mode) : yu::iov_mode_ok(mode))) return "";
+  if (fill && !(dg ? yu::iov_dg_mode_tx(mode) : yu::iov_mode_tx(mode))) return "";
+  return (pack ? yu::plan_iov_pack : yu::plan_iov)(n, mode, fill != 0, 256, yu::env_knobs()).name;
 }
 
 // Completion signal for the host path's direct mode (yucsum_internal.h):
@@ -3546,69 +3503,69 @@ int yu_csum_fill_ragged(uint8_t *data, const uint64_t *offsets, uint64_t n,
 int yu_csum_batch_iov(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode,
                       const uint16_t *initial_arr, uint16_t initial, const uint8_t *addrs,
                       uint16_t *out, void *stream) {
-  return batch_iov(views, first_iov, n, mode, initial_arr, initial, addrs, out, false, stream);
+  return call_iov({false, false, views, first_iov, n, mode, initial_arr, initial, addrs, nullptr, nullptr, out,
+                   false, stream});
 }
 
 int yu_csum_fill_iov(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode,
                      const uint16_t *initial_arr, uint16_t initial, const uint8_t *addrs,
                      uint16_t *out, void *stream) {
-  return batch_iov(views, first_iov, n, mode, initial_arr, initial, addrs, out, true, stream);
+  return call_iov({false, false, views, first_iov, n, mode, initial_arr, initial, addrs, nullptr, nullptr, out,
+                   true, stream});
 }
 
 const char *yu_iov_variant_n(int mode, uint64_t n, int fill) {
-  if (mode < 0 || mode >= YU_MODE_COUNT || !yu::iov_mode_ok(mode)) return "";
-  if (fill && !yu::iov_mode_tx(mode)) return "";
-  return yu::plan_iov(n, mode, fill != 0, 256, yu::env_knobs()).name;
+  return iov_variant(false, false, mode, n, fill);
 }
 
 int yu_csum_batch_iov_datagram(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode,
                                uint16_t *out, void *stream) {
-  return batch_iov_datagram(views, first_iov, n, mode, out, false, stream);
+  return call_iov({true, false, views, first_iov, n, mode, nullptr, 0, nullptr, nullptr, nullptr, out, false,
+                   stream});
 }
 
 int yu_csum_fill_iov_datagram(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode,
                               uint16_t *out, void *stream) {
-  return batch_iov_datagram(views, first_iov, n, mode, out, true, stream);
+  return call_iov({true, false, views, first_iov, n, mode, nullptr, 0, nullptr, nullptr, nullptr, out, true,
+                   stream});
 }
 
 const char *yu_iov_datagram_variant_n(int mode, uint64_t n, int fill) {
-  if (mode < 0 || mode >= YU_MODE_COUNT || !yu::iov_dg_mode_ok(mode)) return "";
-  if (fill && !yu::iov_dg_mode_tx(mode)) return "";
-  return yu::plan_iov(n, mode, fill != 0, 256, yu::env_knobs()).name;
+  return iov_variant(true, false, mode, n, fill);
 }
 
 int yu_csum_pack_iov(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode,
                      const uint16_t *initial_arr, uint16_t initial, const uint8_t *addrs, uint8_t *dst,
                      const uint64_t *dst_offsets, uint16_t *out, void *stream) {
-  return pack_iov(views, first_iov, n, mode, initial_arr, initial, addrs, dst, dst_offsets, out, false, stream);
+  return call_iov({false, true, views, first_iov, n, mode, initial_arr, initial, addrs, dst, dst_offsets, out,
+                   false, stream});
 }
 
 int yu_csum_pack_fill_iov(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode,
                           const uint16_t *initial_arr, uint16_t initial, const uint8_t *addrs, uint8_t *dst,
                           const uint64_t *dst_offsets, uint16_t *out, void *stream) {
-  return pack_iov(views, first_iov, n, mode, initial_arr, initial, addrs, dst, dst_offsets, out, true, stream);
+  return call_iov({false, true, views, first_iov, n, mode, initial_arr, initial, addrs, dst, dst_offsets, out,
+                   true, stream});
 }
 
 const char *yu_iov_pack_variant_n(int mode, uint64_t n, int fill) {
-  if (mode < 0 || mode >= YU_MODE_COUNT || !yu::iov_mode_ok(mode)) return "";
-  if (fill && !yu::iov_mode_tx(mode)) return "";
-  return yu::plan_iov_pack(n, mode, fill != 0, 256, yu::env_knobs()).name;
+  return iov_variant(false, true, mode, n, fill);
 }
 
 int yu_csum_pack_iov_datagram(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode,
                               uint8_t *dst, const uint64_t *dst_offsets, uint16_t *out, void *stream) {
-  return pack_iov_datagram(views, first_iov, n, mode, dst, dst_offsets, out, false, stream);
+  return call_iov({true, true, views, first_iov, n, mode, nullptr, 0, nullptr, dst, dst_offsets, out, false,
+                   stream});
 }
 
 int yu_csum_pack_fill_iov_datagram(const yu_iovec *views, const uint64_t *first_iov, uint64_t n, int mode,
                                    uint8_t *dst, const uint64_t *dst_offsets, uint16_t *out, void *stream) {
-  return pack_iov_datagram(views, first_iov, n, mode, dst, dst_offsets, out, true, stream);
+  return call_iov({true, true, views, first_iov, n, mode, nullptr, 0, nullptr, dst, dst_offsets, out, true,
+                   stream});
 }
 
 const char *yu_iov_pack_datagram_variant_n(int mode, uint64_t n, int fill) {
-  if (mode < 0 || mode >= YU_MODE_COUNT || !yu::iov_dg_mode_ok(mode)) return "";
-  if (fill && !yu::iov_dg_mode_tx(mode)) return "";
-  return yu::plan_iov_pack(n, mode, fill != 0, 256, yu::env_knobs()).name;
+  return iov_variant(true, true, mode, n, fill);
 }
 
 const char *yu_uniform_variant(uint64_t stride, uint32_t len, int mode,
