@@ -83,12 +83,14 @@ extern "C" {
 /*                  but UDP, TCP and ICMP;                               */
 /*                  yu_csum_fill_iov_datagram: VERIFY_IPV4, VERIFY_RX.   */
 /*  [side-align]    device calls: initial_arr not 2-byte aligned, addrs  */
-/*                  not 4-byte aligned, out not 2-byte aligned.          */
+/*                  not 4-byte aligned, out not 2-byte aligned           */
+/*                  (yu_tx_build_ragged: out).                           */
 /*  [data]          data == NULL with n > 0 (device calls), h_data ==    */
 /*                  NULL while the packets hold bytes (host calls), iov  */
 /*                  == NULL while first_iov names views; views == NULL  */
 /*                  with n > 0 (yu_csum_*_iov); dst == NULL with n > 0   */
-/*                  (yu_csum_pack_*_iov).                                */
+/*                  (yu_csum_pack_*_iov); payload, recs or dst == NULL   */
+/*                  with n > 0 (yu_tx_build_ragged).                     */
 /*  [len-transport] a packet of a mode other than RAW longer than        */
 /*                  YU_MAX_TRANSPORT_LEN (uniform len; every host ragged */
 /*                  or iov packet). Device ragged batches are not read   */
@@ -103,8 +105,10 @@ extern "C" {
 /*                  yu_csum_*_iov (device tables): first_iov == NULL or  */
 /*                  not 8-byte aligned, views not 8-byte aligned;        */
 /*                  yu_csum_pack_*_iov: also dst_offsets == NULL or not  */
+/*                  8-byte aligned; yu_tx_build_ragged: pay_offsets or   */
+/*                  dst_offsets == NULL or not 8-byte aligned, recs not  */
 /*                  8-byte aligned.                                      */
-/*  [iov-view]     a view with base == NULL and len > 0.                */
+/*  [iov-view]    a view with base == NULL and len > 0.                */
 /*  [fill-align]    yu_csum_fill_uniform: data or stride not a multiple  */
 /*                  of 4. The uniform writers store whole dwords of each */
 /*                  packet's window, so no dword may hold bytes of two   */
@@ -596,6 +600,92 @@ int yu_csum_pack_fill_iov_datagram(const yu_iovec *views, const uint64_t *first_
                                    uint64_t n, int mode, uint8_t *dst,
                                    const uint64_t *dst_offsets, uint16_t *out, void *stream);
 
+/* Outgoing IPv4 datagrams built on the device. The reference's senders never
+ * hold a packet whose headers somebody else encoded: sendUDP
+ * (transport/udp/endpoint.go:164-187), sendTCP / sendTCPWithOptions
+ * (transport/tcp/connect.go:556-586, 288-322) and sendICMPv4
+ * (network/ipv4/icmp.go:36-45) are handed a payload and a few numbers, encode
+ * the transport header into a zeroed Prependable, sum the payload, store the
+ * transport field and call WritePacket (network/ipv4/ipv4.go:80-97), which
+ * encodes and sums the IPv4 header; the link endpoint writes header and payload
+ * as one wire image. yu_tx_build_ragged is that composition for a batch: it
+ * takes the payloads and one fixed-size record per packet and writes whole
+ * datagrams with both checksum fields. No header is read: there is no view
+ * table, no header gather and no parse, the header sums are arithmetic on the
+ * record, and each packet has exactly one source range.
+ *
+ * One outgoing datagram's header fields: 32 bytes, 8-byte aligned, DEVICE
+ * memory. Numbers are host byte order (as `out` is); addresses are wire bytes. */
+typedef struct yu_tx_record {
+  uint8_t  src[4], dst[4];   /* IPv4Fields.SrcAddr / DstAddr                     */
+  uint16_t sport, dport;     /* TCP/UDP ports. ICMP: sport = type << 8 | code,   */
+                             /*                      dport ignored               */
+  uint32_t seq, ack;         /* TCP only                                         */
+  uint16_t window;           /* TCP only (the caller clamps, connect.go:559-561) */
+  uint8_t  flags;            /* TCP only                                         */
+  uint8_t  doff;             /* TCP only: header bytes incl. options, 20..60, %4 */
+  uint8_t  proto;            /* 6, 17, 1; any other value: no transport header   */
+  uint8_t  ttl;              /* WritePacket: 64                                  */
+  uint16_t ip_id;            /* WritePacket: 0                                   */
+  uint8_t  tos;              /* 0                                                */
+  uint8_t  reserved;         /* 0                                                */
+  uint16_t frag;             /* flags/fragment-offset word as a number; 0        */
+} yu_tx_record;
+
+/* Call discipline: that of the other device calls. Every pointer is a DEVICE
+ * pointer; asynchronous on `stream`, no allocation, no synchronisation,
+ * graph-capturable, YU_ENODEV without a device, n == 0 a no-op returning YU_OK
+ * after the checks that do not need n.
+ *
+ * Input: payload i is payload[pay_offsets[i], pay_offsets[i+1]), the ragged
+ * layout (n + 1 DEVICE uint64 offsets, 8-byte aligned), any byte alignment; L is
+ * its length. For TCP the payload's first doff - 20 bytes are the option bytes,
+ * as sendTCPWithOptions prepends them. `recs` holds n records.
+ *
+ * Output: datagram i is stored at dst[dst_offsets[i], dst_offsets[i] + T).
+ * `dst`, `dst_offsets`, slack, room and "overlaps nothing the call reads" are
+ * yu_csum_pack_iov's, word for word. With H the transport header's length (TCP
+ * 20, UDP 8, ICMP 4, any other protocol 0), T = 20 + H + L, and the image is
+ *   bytes 0..19 (IPv4.Encode, header/ipv4.go:146-157, IHL 5):
+ *     0x45, tos, BE16(T), BE16(ip_id), BE16(frag), ttl, proto, BE16(ipsum), src, dst
+ *   TCP (TCP.Encode, header/tcp.go:176-186): BE16 sport, BE16 dport, BE32 seq,
+ *     BE32 ack, (doff / 4) << 4, flags, BE16 window, BE16 xsum, 0, 0, the payload
+ *   UDP (header/udp.go:78-83): BE16 sport, BE16 dport, BE16(8 + L), BE16 xsum,
+ *     the payload
+ *   ICMP: sport >> 8, sport & 0xFF, BE16 xsum, the payload
+ *   any other protocol: the payload follows the IPv4 header directly.
+ * The two fields are defined by the image itself: ipsum is YU_MODE_IPV4's value,
+ * xsum YU_MODE_TX_DATAGRAM's second value for this image with both fields taken
+ * as 0. So with tight offsets yu_csum_fill_ragged(TX_DATAGRAM) on the result
+ * changes no byte; a UDP sum of 0x0000 is stored as 0x0000 (no 0xFFFF
+ * substitution) and an all-zero ICMP segment gets 0xFFFF, as in the reference.
+ * `out` may be NULL; otherwise out[2i], out[2i+1] = {ipsum, xsum} as TX_DATAGRAM
+ * gives them (other protocols: xsum 0).
+ *
+ * In contract: T <= 65535; T <= dst_offsets[i+1] - dst_offsets[i], offsets
+ * non-decreasing on both sides; TCP: 20 <= doff <= 60, doff % 4 == 0 and
+ * doff - 20 <= L. The tables are device memory and are not read on the host, so
+ * an out-of-contract packet gets the pack calls' rule: its bytes are
+ * unspecified inside its own span [dst_offsets[i], min(dst_offsets[i+1],
+ * dst_offsets[n])) only and its out pair is unspecified; never a fault or a
+ * hang. A TCP record whose only fault is doff gets every byte exact except the
+ * two transport-field bytes. Every other packet is exact, and nothing outside
+ * dst[0, dst_offsets[n]) is written.
+ *
+ * Reads and writes: every payload byte read lies in the dwords that hold
+ * payload[0, pay_offsets[n]); record reads are recs[0, n). Every byte of a
+ * datagram is stored by exactly one store, never a read-modify-write (with
+ * tight packing the rest of a dword belongs to another wave's packet); slack is
+ * never written. The header is stored last, once, with both fields in place.
+ *
+ * YU_EINVAL (Preconditions above): [data]: payload, recs or dst NULL with
+ * n > 0; [offsets]: pay_offsets or dst_offsets NULL or not 8-byte aligned, recs
+ * not 8-byte aligned; [side-align]: out not 2-byte aligned. */
+int yu_tx_build_ragged(const uint8_t *payload, const uint64_t *pay_offsets,
+                       const yu_tx_record *recs, uint64_t n,
+                       uint8_t *dst, const uint64_t *dst_offsets,
+                       uint16_t *out, void *stream);
+
 /* Host-memory field writer: the matching yu_csum_batch_host_* call (TX modes
  * UDP/TCP/IPV4/ICMP/TX_DATAGRAM only), then each result stored big-endian into the
  * packet's checksum field in host memory, as the device writer does
@@ -734,6 +824,9 @@ const char *yu_iov_pack_variant_n(int mode, uint64_t n, int fill);
 /* The same for the packing whole-datagram calls (fill != 0:
  * yu_csum_pack_fill_iov_datagram). */
 const char *yu_iov_pack_datagram_variant_n(int mode, uint64_t n, int fill);
+/* The kernel variant yu_tx_build_ragged launches for a batch of n packets. No
+ * device needed. */
+const char *yu_tx_build_variant_n(uint64_t n);
 
 #ifdef __cplusplus
 }

@@ -20,6 +20,7 @@ EXPORTS = (
     "yu_csum_batch_iov_datagram", "yu_csum_fill_iov_datagram", "yu_iov_datagram_variant_n",
     "yu_csum_pack_iov", "yu_csum_pack_fill_iov", "yu_iov_pack_variant_n",
     "yu_csum_pack_iov_datagram", "yu_csum_pack_fill_iov_datagram", "yu_iov_pack_datagram_variant_n",
+    "yu_tx_build_ragged", "yu_tx_build_variant_n",
     "yu_csum_batch_host_uniform", "yu_csum_batch_host_ragged", "yu_csum_batch_host_iov",
     "yu_csum_batch_host_uniform_multi", "yu_csum_batch_host_ragged_multi",
     "yu_csum_batch_host_iov_multi",
@@ -42,6 +43,15 @@ YU_OK, YU_EINVAL, YU_ENODEV, YU_ENOMEM, YU_EHIP_BASE = 0, -22, -19, -12, -1000
 class YuIovec(ctypes.Structure):
     """struct yu_iovec (include/yucsum.h): one view of a scatter-gather packet."""
     _fields_ = [("base", ctypes.c_void_p), ("len", ctypes.c_uint64)]
+
+
+class YuTxRecord(ctypes.Structure):
+    """struct yu_tx_record (include/yucsum.h): one outgoing datagram's header fields."""
+    _fields_ = [("src", ctypes.c_uint8 * 4), ("dst", ctypes.c_uint8 * 4), ("sport", ctypes.c_uint16),
+                ("dport", ctypes.c_uint16), ("seq", ctypes.c_uint32), ("ack", ctypes.c_uint32),
+                ("window", ctypes.c_uint16), ("flags", ctypes.c_uint8), ("doff", ctypes.c_uint8),
+                ("proto", ctypes.c_uint8), ("ttl", ctypes.c_uint8), ("ip_id", ctypes.c_uint16),
+                ("tos", ctypes.c_uint8), ("reserved", ctypes.c_uint8), ("frag", ctypes.c_uint16)]
 
 
 class YuError(RuntimeError):
@@ -147,6 +157,10 @@ def lib() -> ctypes.CDLL:
         f.argtypes = [vp, vp, u64, i32, vp, vp, vp, vp]
     L.yu_iov_pack_datagram_variant_n.restype = c.c_char_p
     L.yu_iov_pack_datagram_variant_n.argtypes = [i32, u64, i32]
+    L.yu_tx_build_ragged.restype = i32
+    L.yu_tx_build_ragged.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp]
+    L.yu_tx_build_variant_n.restype = c.c_char_p
+    L.yu_tx_build_variant_n.argtypes = [u64]
     L.yu_host_contexts.restype = i32
     L.yu_host_contexts.argtypes = []
     L.yu_host_staging_bytes.restype = u64

@@ -3,7 +3,7 @@
 Thin Python front end over the C ABI's batched entry points
 (``yu_csum_batch_uniform`` / ``yu_csum_batch_ragged`` / ``yu_csum_batch_iov`` /
 ``yu_csum_batch_iov_datagram`` / ``yu_csum_pack_iov`` / ``yu_csum_pack_iov_datagram`` / ``yu_csum_fill_*`` /
-``yu_csum_batch_host_uniform``,
+``yu_tx_build_ragged`` / ``yu_csum_batch_host_uniform``,
 include/yucsum.h). PyTorch is used only for device
 memory and streams: the arithmetic happens in the hand-written gfx950 kernels of
 ``csrc/yucsum_kernels.hip``. There is no CPU fallback — without a HIP device every
@@ -433,6 +433,99 @@ def pack_iov_datagrams(pools, view_pool: torch.Tensor, view_off: torch.Tensor, v
                              out.data_ptr() if n else None, s))
     out.iov_table = (table, fi, do)
     return out, dst, (do if dst_offsets is None else dst_offsets)
+
+
+def build_datagrams(payload: torch.Tensor, pay_offsets: torch.Tensor, records: torch.Tensor, *,
+                    dst: torch.Tensor | None = None, dst_offsets: torch.Tensor | None = None,
+                    out: torch.Tensor | None = None, validate: bool = False,
+                    stream: torch.cuda.Stream | None = None):
+    """Outgoing IPv4 datagrams built on the device (yu_tx_build_ragged): what sendUDP,
+    sendTCP / sendTCPWithOptions and sendICMPv4 do with a payload and a few numbers,
+    WritePacket's IPv4 header included. Payload i is ``payload[pay_offsets[i] :
+    pay_offsets[i+1]]`` (n+1 int64/uint64 offsets; for TCP its first ``doff - 20`` bytes
+    are the option bytes); ``records`` is a device uint8 tensor of shape (n, 32), one
+    ``yu_tx_record`` per packet (:func:`yustack_amd.packets.tx_records` fills them on the
+    host). Returns ``(dst, dst_offsets, out)``: datagram i, 20 + H + L bytes with both
+    checksum fields in place, lies at ``dst[dst_offsets[i]:]``, and ``out[2i], out[2i+1]``
+    are its IPv4 and transport field values as ``tx_datagram`` gives them.
+
+    ``dst_offsets=None``: the tight offsets, ``pay_offsets + exclusive_cumsum(20 + H)``
+    with H from the records' proto column, computed on the device with no host read;
+    ``(dst, dst_offsets)`` is then the batch :func:`checksum_ragged` takes. ``dst=None``:
+    a new tensor of ``dst_offsets[-1]`` bytes (one synchronisation to learn the size).
+    ``validate=True`` reads the tables back and raises ValueError for any packet out of
+    the call's contract (include/yucsum.h). With ``dst``, ``dst_offsets`` and ``out``
+    given the call is capturable in a graph."""
+    _dev_u8(payload, "payload")
+    dev = payload.device
+    _dev_u8(records, "records")
+    if records.device != dev:
+        raise TypeError(f"records must be on {dev}")
+    if records.dim() != 2 or records.shape[1] != 32:
+        raise ValueError("records must have shape (n, 32)")
+    n = records.shape[0]
+    po = _dev_index(pay_offsets, "pay_offsets", dev, n + 1)
+    if records.data_ptr() % 8 or po.data_ptr() % 8:
+        raise TypeError("records and pay_offsets must be 8-byte aligned")
+    if dst is not None:
+        _dev_u8(dst, "dst")
+        if dst.device != dev:
+            raise TypeError(f"dst must be on {dev}")
+        if _overlaps(dst, payload) or _overlaps(dst, records):
+            raise ValueError("dst overlaps payload or records")
+    need_len = dst_offsets is None or (validate and n > 0)
+    if need_len:  # 20 + H per packet, from the proto column
+        proto = records[:, 24].to(torch.int64)
+        hdr = 20 + 20 * (proto == 6) + 8 * (proto == 17) + 4 * (proto == 1)
+    if dst_offsets is None:
+        do = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        if n:
+            do[1:] = torch.cumsum(hdr, 0)
+        do += po
+    else:
+        do = _dev_index(dst_offsets, "dst_offsets", dev, n + 1)
+        if do.data_ptr() % 8:
+            raise TypeError("dst_offsets must be 8-byte aligned")
+    if dst is None:
+        dst = torch.empty(max(int(do[-1].item()), 1), dtype=torch.uint8, device=dev)
+    if validate and n > 0:
+        plen = po[1:] - po[:-1]
+        room = do[1:] - do[:-1]
+        total = hdr + plen
+        doff = records[:, 23].to(torch.int64)
+        tcp_ok = (proto != 6) | ((doff >= 20) & (doff <= 60) & (doff % 4 == 0) & (doff - 20 <= plen))
+        ok = torch.stack(((plen >= 0).all() & (po[0] >= 0) & (po[-1] <= payload.numel()),
+                          (room >= 0).all() & (do[0] >= 0) & (do[-1] <= dst.numel()),
+                          (total <= MAX_TRANSPORT_LEN).all(), (total <= room).all(), tcp_ok.all())).tolist()
+        if not ok[0]:
+            raise ValueError("pay_offsets is not non-decreasing within payload")
+        if not ok[1]:
+            raise ValueError("dst_offsets is not non-decreasing within dst")
+        if not ok[2]:
+            raise ValueError("datagrams must be <= 65535 bytes")
+        if not ok[3]:
+            raise ValueError("a datagram has less room in dst than bytes")
+        if not ok[4]:
+            raise ValueError("a TCP record's doff is not 20..60, a multiple of 4 and within its payload")
+    if out is None:
+        out = torch.empty(max(2 * n, 1), dtype=torch.uint16, device=dev)[:2 * n]
+    else:
+        _opt(out, torch.uint16, 2 * n, dev, "out")
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream(dev))
+        for t in (po, do, dst, out):
+            t.record_stream(stream)
+    with torch.cuda.device(dev):
+        rc = lib().yu_tx_build_ragged(payload.data_ptr(), po.data_ptr(), records.data_ptr(), n, dst.data_ptr(),
+                                      do.data_ptr(), out.data_ptr() if n else None, _stream(dev, stream))
+    check(rc, "yu_tx_build_ragged")
+    out.build_tables = (po, do)  # the kernel reads them asynchronously: keep them alive with the result
+    return dst, (do if dst_offsets is None else dst_offsets), out
+
+
+def build_variant(n: int = 1 << 20) -> str:
+    """Name of the kernel :func:`build_datagrams` launches for a batch of n packets."""
+    return lib().yu_tx_build_variant_n(n).decode()
 
 
 def iov_pack_datagram_variant(mode="verify_rx", n: int = 1 << 20, fill: bool = False) -> str:

@@ -83,17 +83,23 @@
 //     (yu_csum_pack_iov_datagram / yu_csum_pack_fill_iov_datagram): k_iov's header
 //     gather, parse and epilogue, k_pack's store side over the plain walk, the window
 //     [HL, TL) applied to the sum alone.
+//   k_build<U, NT>: yu_tx_build_ragged (planned by yu::plan_build): one wave per
+//     outgoing datagram, the payload as a single view through k_pack's store side,
+//     the header encoded and summed from a 32-byte record and stored last
+//     (yucsum_build.h).
 //   All are grid-stride kernels; the grid is sized per CU and over-subscribed
 //   (see blocks_per_cu in yucsum_plan.cpp), except that k_seg narrows it for
 //   small packets (seg_waves).
 #include <hip/hip_runtime.h>
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include <atomic>
 #include <type_traits>
 
 #include "yucsum.h"
+#include "yucsum_build.h"
 #include "yucsum_dense.h"
 #include "yucsum_internal.h"
 #include "yucsum_iov.h"
@@ -3191,6 +3197,133 @@ __global__ __launch_bounds__(256) void k_pack_dg(const yu_iovec *views_, const u
 }
 
 // ---------------------------------------------------------------------
+// k_build<U, NT>: outgoing IPv4 datagrams built from a payload and one 32-byte
+// record per packet (yu_tx_build_ragged; yucsum_build.h has the arithmetic). One
+// wave per packet on the over-subscribed grid, as k_loop and k_iov. It is
+// k_pack's store side fed by exactly one source range: the payload is a single
+// view, walked from packet offset 20 + H in steps of U 1-KiB slots, each summed
+// (k_iov's slot sum) and stored through yucsum_iov_pack.h's plan, shift and
+// masked stores with nothing held back. There is no view table, no gather and
+// no parse: the control data of a packet is its pay_offsets pair, its
+// dst_offsets pair and its record (two 16-byte loads), all wave-uniform scalar
+// loads through the constant address space (no store of the call may touch the
+// tables) issued a packet ahead. The header's sums are arithmetic on the
+// record; when the payload's class sums are known the header's 20 + H bytes are
+// encoded with both fields in place and stored last, once: lane J < 11 owns
+// destination dword J of the packet (source dwords J - 1 and J, the neighbour's
+// by one DPP row shift), masked to the header's end and the packet's room and
+// stored by the width rules of a payload dword.
+// ---------------------------------------------------------------------
+struct BuildArgs {
+  uint8_t *dst;
+  const uint64_t *dst_offsets;
+  uint16_t *out;
+  uint64_t n;
+};
+
+struct BuildPkt {
+  uint64_t p0, p1;  // pay_offsets[q], pay_offsets[q + 1]
+  uint64_t o0, o1;  // dst_offsets[q], dst_offsets[q + 1]
+  yu::BuildRec R;
+};
+
+template <int U, int NT>
+__global__ __launch_bounds__(256) void k_build(const uint8_t *payload, const uint64_t *pay_offsets_,
+                                               const yu_tx_record *recs_, BuildArgs A) {
+  const YU_CONST_AS uint64_t *pay_offsets = const_as(pay_offsets_);
+  const YU_CONST_AS uint64_t *dst_offsets = const_as(A.dst_offsets);
+  const YU_CONST_AS uint32_t *recs = const_as((const uint32_t *)recs_);
+  const uint32_t lane = threadIdx.x & 63u;
+  const bool lead = lane == 63;
+  const uint64_t wave = grid_wave(0u);
+  const uint64_t nwave = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  if (wave >= A.n) return;
+  const uint64_t poN = pay_offsets[A.n], doN = dst_offsets[A.n];
+
+  // Packet q's control data (past the batch: packet 0's again, never used).
+  auto packet = [&](BuildPkt &P, uint64_t q) __attribute__((always_inline)) {
+    const uint64_t i = q < A.n ? q : 0;
+    P.p0 = pay_offsets[i];
+    P.p1 = pay_offsets[i + 1];
+    P.o0 = dst_offsets[i];
+    P.o1 = dst_offsets[i + 1];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) P.R.w[k] = recs[8 * i + k];
+  };
+
+  const PackStore st;
+  BuildPkt cur, nx;
+  packet(cur, wave);
+  for (uint64_t p = wave; p < A.n; p += nwave) {
+    packet(nx, p + nwave);
+    const yu::BuildRec R = cur.R;
+    const uint32_t H = yu::build_l4_len(yu::build_proto(R));
+    // the payload, cut to payload[0, pay_offsets[n]) whatever its offsets say
+    const bool ranged = cur.p0 <= cur.p1 && cur.p1 <= poN;
+    const uint64_t pe = cur.p1 < poN ? cur.p1 : poN;
+    const uint64_t plen = pe > cur.p0 ? pe - cur.p0 : 0;
+    const uint64_t addr = (uint64_t)(uintptr_t)payload + (plen ? cur.p0 : 0);
+    const yu::IovPackDst D = {(uint64_t)(uintptr_t)A.dst + cur.o0, yu::iov_pack_room(cur.o0, cur.o1, doN)};
+    yu::IovWalk W;
+    yu::iov_walk_reset(W);
+    W.off = yu::kBuildIp + H;
+    const int32_t vpk = yu::iov_pack_view(addr, W.off);
+    yu::iov_walk_view(W, addr, plen, false, 0u);
+    const uint32_t L = W.off - (yu::kBuildIp + H);  // the bytes taken: T <= 65535
+
+    uint32_t accA = 0, accB = 0;
+    uint32_t cprev = 0;  // lane 63: the last source dword of the slot before
+    while (!yu::iov_walk_done(W)) {
+      uint32_t info[U];
+      int32_t po[U];
+      uint4 c[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        po[u] = yu::iov_pack_po(vpk, W.w, lane);
+        yu::IovSlot S;
+        yu::iov_walk_slot(W, S);
+        info[u] = S.info;
+        c[u] = iov_slot_load<NT>(S, lane, u);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (yu::iov_lim(info[u]) == 0) continue;  // an empty slot (wave-uniform)
+        const uint32_t t = iov_slot_sum(c[u], info[u], lane);
+        const bool swap = (info[u] & yu::kIovSwap) != 0;
+        yu::IovPackPlan P;
+        yu::iov_pack_plan(P, info[u], D, po[u], lane);
+        const uint32_t prev = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(4u * ((lane - 1u) & 63u)),
+                                                                     (int)(lead ? cprev : c[u].w));
+        yu::iov_pack_lane(st, P, lane, c[u].x, c[u].y, c[u].z, c[u].w, prev, -1, -1);
+        cprev = c[u].w;
+        accA += swap ? t : 0u;
+        accB += swap ? 0u : t;
+      }
+    }
+    const uint32_t sA = (uint32_t)__builtin_amdgcn_readlane((int)group_total<64>(accA), 63);
+    const uint32_t sB = (uint32_t)__builtin_amdgcn_readlane((int)group_total<64>(accB), 63);
+    uint32_t ipsum, xsum;
+    yu::build_values(R, H, L, sA, sB, ipsum, xsum);
+
+    // the header, stored last: lane J's destination dword J
+    {
+      const uint32_t hw = yu::build_hdr_src(R, H, L, ipsum, xsum, lane);
+      const uint32_t hprev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hw, 0x111, 0xf, 0xf, true);  // row_shr:1
+      yu::IovPackPlan P;
+      yu::build_hdr_plan(P, D, H);
+      const uint32_t m = lane < yu::kBuildHdrDwords ? yu::iov_pack_mask(P, lane) : 0u;
+      if (m) yu::iov_pack_store(st, (P.pa & ~3ull) + 4u * lane, yu::build_hdr_dst(hw, hprev, P.delta), m);
+    }
+    if (lead && A.out) {
+      const bool ok = yu::build_in_contract(R, ranged, W.over != 0u, L, D.room);
+      A.out[2 * p] = (uint16_t)(ok ? ipsum : 0u);
+      A.out[2 * p + 1] = (uint16_t)(ok ? xsum : 0u);
+    }
+    cur = nx;
+  }
+}
+
+// ---------------------------------------------------------------------
 // Host side: launch. Which kernel, form, load policy and grid a batch gets is
 // yu::plan's decision (yucsum_plan.cpp); here are the functions it names.
 // ---------------------------------------------------------------------
@@ -3446,6 +3579,47 @@ const char *iov_variant(bool dg, bool pack, int mode, uint64_t n, int fill) {
   return (pack ? yu::plan_iov_pack : yu::plan_iov)(n, mode, fill != 0, 256, yu::env_knobs()).name;
 }
 
+// yu_tx_build_ragged: the record as the kernel reads it (eight little-endian
+// dwords, yu::BuildRec), its arguments, then the device's plan and the launch.
+static_assert(sizeof(yu_tx_record) == 32, "yu_tx_record is 32 bytes");
+static_assert(offsetof(yu_tx_record, src) == 0, "yu_tx_record.src");
+static_assert(offsetof(yu_tx_record, dst) == 4, "yu_tx_record.dst");
+static_assert(offsetof(yu_tx_record, sport) == 8, "yu_tx_record.sport");
+static_assert(offsetof(yu_tx_record, dport) == 10, "yu_tx_record.dport");
+static_assert(offsetof(yu_tx_record, seq) == 12, "yu_tx_record.seq");
+static_assert(offsetof(yu_tx_record, ack) == 16, "yu_tx_record.ack");
+static_assert(offsetof(yu_tx_record, window) == 20, "yu_tx_record.window");
+static_assert(offsetof(yu_tx_record, flags) == 22, "yu_tx_record.flags");
+static_assert(offsetof(yu_tx_record, doff) == 23, "yu_tx_record.doff");
+static_assert(offsetof(yu_tx_record, proto) == 24, "yu_tx_record.proto");
+static_assert(offsetof(yu_tx_record, ttl) == 25, "yu_tx_record.ttl");
+static_assert(offsetof(yu_tx_record, ip_id) == 26, "yu_tx_record.ip_id");
+static_assert(offsetof(yu_tx_record, tos) == 28, "yu_tx_record.tos");
+static_assert(offsetof(yu_tx_record, reserved) == 29, "yu_tx_record.reserved");
+static_assert(offsetof(yu_tx_record, frag) == 30, "yu_tx_record.frag");
+
+typedef void (*BuildFn)(const uint8_t *, const uint64_t *, const yu_tx_record *, BuildArgs);
+const BuildFn kBuildFns[yu::kBuildKernelCount][3] = {
+    {k_build<4, 0>, k_build<4, 1>, k_build<4, 2>},
+};
+
+int tx_build(const uint8_t *payload, const uint64_t *pay_offsets, const yu_tx_record *recs, uint64_t n,
+             uint8_t *dst, const uint64_t *dst_offsets, uint16_t *out, void *stream) {
+  if (out && !aligned(out, 2)) return YU_EINVAL;  // EINVAL:side-align
+  if (n == 0) return YU_OK;
+  if (!pay_offsets || !aligned(pay_offsets, 8) || !dst_offsets || !aligned(dst_offsets, 8) || !aligned(recs, 8))
+    return YU_EINVAL;  // EINVAL:offsets
+  if (!payload || !recs || !dst) return YU_EINVAL;  // EINVAL:data
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return hip_status(e);
+  const yu::BuildPlan p = yu::plan_build(n, cu_count(dev), yu::env_knobs());
+  const BuildArgs a = {dst, dst_offsets, out, n};
+  hipLaunchKernelGGL(kBuildFns[p.kernel][p.policy], dim3(p.blocks), dim3(256), 0, (hipStream_t)stream, payload,
+                     pay_offsets, recs, a);
+  return hip_status(hipGetLastError());
+}
+
 // Completion signal for the host path's direct mode (yucsum_internal.h):
 // stored after the work before it on the stream, with system-scope release,
 // into coherent pinned host memory.
@@ -3566,6 +3740,15 @@ int yu_csum_pack_fill_iov_datagram(const yu_iovec *views, const uint64_t *first_
 
 const char *yu_iov_pack_datagram_variant_n(int mode, uint64_t n, int fill) {
   return iov_variant(true, true, mode, n, fill);
+}
+
+int yu_tx_build_ragged(const uint8_t *payload, const uint64_t *pay_offsets, const yu_tx_record *recs, uint64_t n,
+                       uint8_t *dst, const uint64_t *dst_offsets, uint16_t *out, void *stream) {
+  return tx_build(payload, pay_offsets, recs, n, dst, dst_offsets, out, stream);
+}
+
+const char *yu_tx_build_variant_n(uint64_t n) {
+  return yu::plan_build(n, 256, yu::env_knobs()).name;
 }
 
 const char *yu_uniform_variant(uint64_t stride, uint32_t len, int mode,

@@ -321,4 +321,20 @@ IovPlan plan_iov_pack(uint64_t n, int mode, bool fill, int cus, const Knobs &k) 
   return p;
 }
 
+// k_build: a wave per packet on the same over-subscribed grid (64 blocks per
+// CU, YU_BLOCKS_PER_CU overrides); the payload is read once, so the load policy
+// is k_iov's (YU_NT's, else slot 2).
+BuildPlan plan_build(uint64_t n, int cus, const Knobs &k) {
+  BuildPlan p;
+  p.kernel = k_build4;
+  p.name = "k_build<4>";
+  p.policy = (uint8_t)(k.nt >= 0 ? k.nt : 2);
+  const uint64_t cap = (uint64_t)cus * (k.blocks_per_cu ? k.blocks_per_cu : 64u);
+  uint64_t blocks = (n + 3) / 4;  // 4 waves per block, a wave per packet
+  if (blocks > cap) blocks = cap;
+  if (blocks < 1) blocks = 1;
+  p.blocks = (uint32_t)blocks;
+  return p;
+}
+
 }  // namespace yu

@@ -199,6 +199,18 @@ IovPlan plan_iov(uint64_t n, int mode, bool fill, int cus, const Knobs &k);
 // the dg kernels.
 IovPlan plan_iov_pack(uint64_t n, int mode, bool fill, int cus, const Knobs &k);
 
+// yu_tx_build_ragged has a plan of its own too: one kernel, k_build
+// (yucsum_build.h), a wave per packet on k_iov's grid. Not one of YU_KERNELS:
+// no checksum batch ever takes it.
+enum BuildKernel : uint8_t { k_build4, kBuildKernelCount };
+struct BuildPlan {
+  BuildKernel kernel;
+  uint8_t policy;  // load-policy slot, as IovPlan's
+  uint32_t blocks;
+  const char *name;  // what yu_tx_build_variant_n returns
+};
+BuildPlan plan_build(uint64_t n, int cus, const Knobs &k);
+
 }  // namespace yu
 #pragma GCC visibility pop
 

@@ -12,8 +12,14 @@ and the test harnesses' inbound builders:
 
 * :func:`tcp_test_packet` transport/tcp/testing/context/context.go:164-209 (SendPacket)
 * :func:`udp_test_packet` transport/udp/udp_test.go:105-144 (sendPacket)
+
+and the record layout of the device-side sender, ``batch.build_datagrams``:
+
+* :data:`TX_RECORD`, :func:`tx_records`  struct yu_tx_record (include/yucsum.h)
 """
 from __future__ import annotations
+
+import numpy as np
 
 from .checksum import Checksum
 from .header import (ICMPv4, ICMPv4MinimumSize, IPv4, IPv4MinimumSize, Route, TCP, TCPMinimumSize,
@@ -116,3 +122,33 @@ def udp_test_packet(payload: bytes, src_port: int, dst_port: int,
     xsum = Checksum(payload, xsum)
     u.SetChecksum(~u.CalculateChecksum(xsum, length) & 0xFFFF)
     return buf
+
+
+# struct yu_tx_record (include/yucsum.h): one outgoing datagram's header fields for
+# batch.build_datagrams. Numbers in host byte order, addresses as wire bytes.
+TX_RECORD = np.dtype([("src", np.uint8, (4,)), ("dst", np.uint8, (4,)), ("sport", np.uint16), ("dport", np.uint16),
+                      ("seq", np.uint32), ("ack", np.uint32), ("window", np.uint16), ("flags", np.uint8),
+                      ("doff", np.uint8), ("proto", np.uint8), ("ttl", np.uint8), ("ip_id", np.uint16),
+                      ("tos", np.uint8), ("reserved", np.uint8), ("frag", np.uint16)])
+assert TX_RECORD.itemsize == 32
+
+
+def tx_records(n: int, *, src=0, dst=0, sport=0, dport=0, seq=0, ack=0, window=0, flags=0, doff=20, proto=17,
+               ttl=64, ip_id=0, tos=0, frag=0) -> np.ndarray:
+    """n records of :data:`TX_RECORD`, each field from an array of n values or a scalar
+    broadcast over the batch (``src`` / ``dst``: (n, 4) or (4,) wire bytes, or one
+    address as a big-endian number). The defaults are WritePacket's
+    (network/ipv4/ipv4.go:80-97): TTL 64, ID 0, TOS 0, no fragment word; ``doff`` 20 is
+    a TCP header without options. ICMP: ``sport`` is ``type << 8 | code``. Upload with
+    ``torch.from_numpy(recs.view(np.uint8).reshape(n, 32))``."""
+    recs = np.zeros(n, dtype=TX_RECORD)
+    for name, a in (("src", src), ("dst", dst)):
+        a = np.asarray(a)
+        if a.ndim == 0:  # 0x0A000001 is 10.0.0.1
+            a = np.array([(int(a) >> s) & 0xFF for s in (24, 16, 8, 0)], dtype=np.uint8)
+        recs[name] = np.broadcast_to(a, (n, 4))
+    for name, a in (("sport", sport), ("dport", dport), ("seq", seq), ("ack", ack), ("window", window),
+                    ("flags", flags), ("doff", doff), ("proto", proto), ("ttl", ttl), ("ip_id", ip_id),
+                    ("tos", tos), ("frag", frag)):
+        recs[name] = np.broadcast_to(np.asarray(a), (n,))
+    return recs
