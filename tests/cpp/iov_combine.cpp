@@ -12,55 +12,11 @@
 // values, so every (length, mode) still sees thousands of splits. Views sit in exact-size heap
 // blocks rounded out to whole dwords (what the kernel's descriptors allow it to
 // read), so under AddressSanitizer a read past them is a report.
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <random>
-#include <vector>
-
-#include "yucsum.h"
-#include "yucsum_iov.h"
+#include "iov_model.h"
 
 namespace {
 
 constexpr int kU = 4;
-int fails = 0;
-uint64_t checks = 0;
-
-struct View {
-  uint8_t *blk;   // heap block: the dwords holding the view
-  uint64_t addr;  // the view's first byte
-  uint32_t len;
-};
-
-// A view of `len` bytes at an address congruent to `a` mod 4 (malloc returns
-// 16-aligned blocks); empty views get a NULL base when a == 0.
-View place(const uint8_t *src, uint32_t len, uint32_t a) {
-  View v;
-  v.len = len;
-  if (len == 0) {
-    v.blk = nullptr;
-    v.addr = a ? 0x1000u + a : 0;  // never dereferenced
-    return v;
-  }
-  const size_t sz = (a + len + 3u) & ~(size_t)3;
-  v.blk = (uint8_t *)malloc(sz);
-  memset(v.blk, 0xA5, sz);  // what surrounds a view is not zero
-  memcpy(v.blk + a, src, len);
-  v.addr = (uint64_t)(uintptr_t)v.blk + a;
-  return v;
-}
-
-// The dword the kernel's buffer load returns at slot offset cr of a slot with
-// `lim` window bytes: inside the descriptor's ceil4(lim) bytes memory, else 0.
-uint32_t load_dword(const yu::IovSlot &S, uint32_t cr, uint32_t lim) {
-  if (cr >= ((lim + 3u) & ~3u)) return 0;
-  uint32_t x;
-  memcpy(&x, (const void *)(uintptr_t)(S.base + cr), 4);
-  return x;
-}
 
 // The packet's value as k_iov computes it.
 uint32_t kernel_value(const std::vector<View> &views, int mode, bool have_addrs, uint32_t a, uint32_t b,
@@ -111,24 +67,6 @@ uint32_t kernel_value(const std::vector<View> &views, int mode, bool have_addrs,
   fp[0] = W.fp[0];
   fp[1] = W.fp[1];
   return yu::iov_value(mode, yu::iov_residue(A, B), len, have_addrs, a, b, initial);
-}
-
-// The scalar composition over the concatenated bytes (include/yucsum.h modes).
-uint32_t scalar_value(const uint8_t *pkt, uint32_t len, int mode, bool have_addrs, const uint8_t *rec,
-                      uint16_t initial) {
-  if (mode == YU_MODE_RAW) return yu_checksum(pkt, len, initial);
-  std::vector<uint8_t> z(pkt, pkt + len);
-  const uint32_t f = yu::iov_mode_field(mode);
-  if (yu::iov_mode_tx(mode) && len >= f + 2u) z[f] = z[f + 1] = 0;
-  uint16_t x = 0;
-  if (mode != YU_MODE_ICMP) {
-    const uint32_t proto = (mode == YU_MODE_TCP || mode == YU_MODE_VERIFY_TCP) ? 6 : 17;
-    x = have_addrs ? yu_pseudo_header_checksum(proto, rec, 4, rec + 4, 4) : initial;
-    const uint8_t lb[2] = {(uint8_t)(len >> 8), (uint8_t)len};
-    x = yu_checksum(lb, 2, x);
-  }
-  x = yu_checksum(z.data(), len, x);
-  return yu::iov_mode_tx(mode) ? (uint16_t)~x : x;
 }
 
 const int kModes[6] = {YU_MODE_RAW, YU_MODE_UDP, YU_MODE_TCP, YU_MODE_ICMP, YU_MODE_VERIFY_TCP,
@@ -244,7 +182,5 @@ int main() {
     yu::iov_walk_view(W, (uint64_t)(uintptr_t)pkt.data(), 1ull << 40, false, 0);
     if (W.off != yu::kIovLimit || !yu::iov_walk_done(W)) ++fails;
   }
-  if (fails) return 1;
-  printf("%llu packets ok\n", (unsigned long long)checks);
-  return 0;
+  return finish();
 }

@@ -15,51 +15,11 @@
 // descriptors allow it to read), so under AddressSanitizer a read past them is
 // a report. TCP segments inside valid datagrams carry DataOffset 5, the one
 // input condition YU_MODE_TCP makes.
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <random>
-#include <vector>
-
-#include "yucsum.h"
-#include "yucsum_iov.h"
+#include "iov_model.h"
 
 namespace {
 
 constexpr int kU = 4;
-int fails = 0;
-uint64_t checks = 0;
-
-struct View {
-  uint8_t *blk;   // heap block: the dwords holding the view
-  uint64_t addr;  // the view's first byte
-  uint32_t len;
-};
-
-View place(const uint8_t *src, uint32_t len, uint32_t a) {
-  View v;
-  v.len = len;
-  if (len == 0) {
-    v.blk = nullptr;
-    v.addr = a ? 0x1000u + a : 0;  // never dereferenced
-    return v;
-  }
-  const size_t sz = (a + len + 3u) & ~(size_t)3;
-  v.blk = (uint8_t *)malloc(sz);
-  memset(v.blk, 0xA5, sz);  // what surrounds a view is not zero
-  memcpy(v.blk + a, src, len);
-  v.addr = (uint64_t)(uintptr_t)v.blk + a;
-  return v;
-}
-
-uint32_t load_dword(const yu::IovSlot &S, uint32_t cr, uint32_t lim) {
-  if (cr >= ((lim + 3u) & ~3u)) return 0;
-  uint32_t x;
-  memcpy(&x, (const void *)(uintptr_t)(S.base + cr), 4);
-  return x;
-}
 
 struct Result {
   uint32_t r[2];
@@ -138,74 +98,6 @@ Result kernel_value(const std::vector<View> &views, int mode) {
   return R;
 }
 
-// The byte-wise composition over the concatenated bytes (include/yucsum.h: the
-// modes' definitions; the fill rule of yu_csum_fill_ragged). field[k]: the packet
-// offset of field k's first byte, -1 when it is not stored.
-void scalar_value(const uint8_t *p, uint32_t len, int mode, uint32_t r[2], int field[2]) {
-  r[0] = r[1] = 0;
-  field[0] = field[1] = -1;
-  const uint32_t hl = len ? (p[0] & 15u) * 4u : 0u;
-  if (mode == YU_MODE_VERIFY_IPV4) {
-    r[0] = yu_checksum(p, hl < len ? hl : len, 0);
-    return;
-  }
-  if (mode == YU_MODE_IPV4) {
-    uint8_t h[64] = {0};
-    const uint32_t cp = len < 64u ? len : 64u;
-    memcpy(h, p, cp);
-    if (cp >= 12) h[10] = h[11] = 0;
-    r[0] = (uint16_t)~yu_checksum(h, hl < cp ? hl : cp, 0);
-    if ((hl < len ? hl : len) >= 12) field[0] = 10;
-    return;
-  }
-  const uint32_t tl = len >= 4 ? ((uint32_t)p[2] << 8) | p[3] : 0u;
-  const bool valid = len >= 20 && hl <= tl && tl <= len;
-  if (mode == YU_MODE_VERIFY_RX) {
-    if (!valid) {
-      r[0] = YU_RX_INVALID;
-      return;
-    }
-    const uint16_t x = yu_checksum(p, hl, 0);
-    if (x == 0 || x == 0xFFFF) r[0] |= YU_RX_IP_OK;
-    const uint32_t proto = p[9], sl = tl - hl;
-    if (proto == 6 || proto == 17 || proto == 1) {
-      r[0] |= YU_RX_L4;
-      uint16_t xs = 0;
-      if (proto != 1) {
-        xs = yu_pseudo_header_checksum(proto, p + 12, 4, p + 16, 4);
-        const uint8_t lb[2] = {(uint8_t)(sl >> 8), (uint8_t)sl};
-        xs = yu_checksum(lb, 2, xs);
-      }
-      xs = yu_checksum(p + hl, sl, xs);
-      if (xs == 0 || xs == 0xFFFF) r[0] |= YU_RX_L4_OK;
-    }
-    return;
-  }
-  // TX_DATAGRAM
-  if (!valid || hl < 20) return;
-  {
-    uint8_t h[64] = {0};
-    memcpy(h, p, hl);
-    h[10] = h[11] = 0;
-    r[0] = (uint16_t)~yu_checksum(h, hl, 0);
-    field[0] = 10;
-  }
-  const uint32_t proto = p[9], sl = tl - hl;
-  const uint32_t fo = proto == 17 ? 6u : (proto == 6 ? 16u : (proto == 1 ? 2u : 0u));
-  const uint32_t mn = proto == 17 ? 8u : (proto == 6 ? 20u : 4u);
-  if (!fo || sl < mn) return;
-  std::vector<uint8_t> z(p + hl, p + tl);
-  z[fo] = z[fo + 1] = 0;
-  uint16_t xs = 0;
-  if (proto != 1) {
-    xs = yu_pseudo_header_checksum(proto, p + 12, 4, p + 16, 4);
-    const uint8_t lb[2] = {(uint8_t)(sl >> 8), (uint8_t)sl};
-    xs = yu_checksum(lb, 2, xs);
-  }
-  r[1] = (uint16_t)~yu_checksum(z.data(), sl, xs);
-  field[1] = (int)(hl + fo);
-}
-
 const int kModes[4] = {YU_MODE_IPV4, YU_MODE_VERIFY_IPV4, YU_MODE_VERIFY_RX, YU_MODE_TX_DATAGRAM};
 
 void check(const uint8_t *pkt, uint32_t len, const uint32_t *cut, int nv, uint32_t aligns, int mode) {
@@ -241,14 +133,9 @@ void check(const uint8_t *pkt, uint32_t len, const uint32_t *cut, int nv, uint32
   for (auto &v : views) free(v.blk);
 }
 
-// A datagram of len bytes: payload kind 0 random, 1 all 0x00, 2 all 0xFF, then
-// the header fields where the packet holds them.
-std::vector<uint8_t> datagram(std::mt19937_64 &rng, uint32_t len, int kind, uint32_t ihl, uint32_t tl, uint32_t proto) {
-  std::vector<uint8_t> p(len + 1);
-  for (auto &x : p) x = kind == 0 ? (uint8_t)rng() : (kind == 1 ? 0x00 : 0xFF);
-  if (len > 0) p[0] = (uint8_t)(0x40u | ihl);
-  if (len > 3) p[2] = (uint8_t)(tl >> 8), p[3] = (uint8_t)tl;
-  if (len > 9) p[9] = (uint8_t)proto;
+// iov_model.h's datagram; a TCP segment inside a valid one carries DataOffset 5.
+std::vector<uint8_t> datagram5(std::mt19937_64 &rng, uint32_t len, int kind, uint32_t ihl, uint32_t tl, uint32_t proto) {
+  std::vector<uint8_t> p = datagram(rng, len, kind, ihl, tl, proto);
   const uint32_t hl = 4 * ihl;
   if (proto == 6 && len >= 20 && hl >= 20 && hl <= tl && tl <= len && tl - hl >= 20) p[hl + 12] = 0x50;
   return p;
@@ -278,7 +165,7 @@ int main() {
               const uint32_t hl = 4 * ihl;
               const uint32_t span = len + 3 > hl ? len + 3 - hl : 1;  // TL in HL - 1 .. len + 1
               const uint32_t tl = (hl + (uint32_t)(cyc / 7 % span) + 65535u) % 65536u;
-              const auto p = datagram(rng, len, (int)(cyc / 3 % 3), ihl, (cyc % 11 == 0) ? len : tl, kProto[cyc / 2 % 4]);
+              const auto p = datagram5(rng, len, (int)(cyc / 3 % 3), ihl, (cyc % 11 == 0) ? len : tl, kProto[cyc / 2 % 4]);
               check(p.data(), len, cut, nv, nv <= 2 ? r % 16 : (uint32_t)rng() & 0xFF, kModes[cyc % 4]);
             }
           }
@@ -289,7 +176,7 @@ int main() {
       for (uint32_t tl = ihl ? 4 * ihl - 1 : 0; tl <= len + 1; ++tl)
         for (int pi = 0; pi < 4; ++pi)
           for (int kind = 0; kind < 3; ++kind, ++cyc) {
-            const auto p = datagram(rng, len, kind, ihl, tl, kProto[pi]);
+            const auto p = datagram5(rng, len, kind, ihl, tl, kProto[pi]);
             const int nv = 1 + (int)(cyc % 4);
             uint32_t c[3] = {(uint32_t)(rng() % (len + 1)), (uint32_t)(rng() % (len + 1)), (uint32_t)(rng() % (len + 1))};
             if (cyc % 3 == 0) c[0] = (uint32_t)(rng() % ((len < 24 ? len : 24) + 1));  // a cut inside the header
@@ -307,7 +194,7 @@ int main() {
     const uint32_t ihl = it < 8 ? 6u : 5u + it % 11;
     const uint32_t seg = it < 8 ? kSeg[it] : (uint32_t)(rng() % 9001);
     const uint32_t tl = 4 * ihl + seg, len = tl + (it % 3 == 0 || tl == 65535u ? 0 : (uint32_t)(rng() % 40));
-    const auto p = datagram(rng, len, 0, ihl, tl, kProto[it % 3]);
+    const auto p = datagram5(rng, len, 0, ihl, tl, kProto[it % 3]);
     uint32_t c[3] = {(uint32_t)(rng() % (len + 1)), (uint32_t)(rng() % (len + 1)), (uint32_t)(rng() % (len + 1))};
     if (c[0] > c[1]) std::swap(c[0], c[1]);
     if (c[1] > c[2]) std::swap(c[1], c[2]);
@@ -316,7 +203,7 @@ int main() {
     for (int m = 0; m < 4; ++m) check(p.data(), len, cut, 4, (uint32_t)rng() & 0xFF, kModes[m]);
   }
   for (uint32_t proto : kProto) {  // 80 one-byte views, then the rest; 70 empty views first
-    const auto p = datagram(rng, 200, 0, 15, 200, proto);
+    const auto p = datagram5(rng, 200, 0, 15, 200, proto);
     for (int m = 0; m < 4; ++m) {
       std::vector<View> v1, v2;
       for (uint32_t i = 0; i < 80; ++i) v1.push_back(place(p.data() + i, 1, i & 3u));
@@ -353,7 +240,5 @@ int main() {
     yu::iov_walk_view_win(W, (uint64_t)(uintptr_t)pkt.data(), 1ull << 40, 20, 65535, false, 0);
     if (W.off != yu::kIovLimit || !yu::iov_walk_done(W)) ++fails;
   }
-  if (fails) return 1;
-  printf("%llu packets ok\n", (unsigned long long)checks);
-  return 0;
+  return finish();
 }

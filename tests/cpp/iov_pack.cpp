@@ -20,86 +20,13 @@
 // cut pair of the short lengths, the rest cycling. Then: 70 one-byte views, room
 // one byte short, room 0, decreasing offsets, a span cut by dst_offsets[n], and a
 // view that does not fit under 65535 bytes.
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <random>
-#include <vector>
-
-#include "yucsum.h"
-#include "yucsum_iov.h"
+#include "iov_model.h"
 #include "yucsum_iov_pack.h"
 
 namespace {
 
 constexpr int kU = 4;
 constexpr size_t kCanary = 32;
-int fails = 0;
-uint64_t checks = 0;
-
-struct View {
-  uint8_t *blk;
-  uint64_t addr;
-  uint64_t len;
-};
-
-View place(const uint8_t *src, uint32_t len, uint32_t a) {
-  View v;
-  v.len = len;
-  if (len == 0) {
-    v.blk = nullptr;
-    v.addr = a ? 0x1000u + a : 0;  // never dereferenced
-    return v;
-  }
-  const size_t sz = (a + len + 3u) & ~(size_t)3;
-  v.blk = (uint8_t *)malloc(sz);
-  memset(v.blk, 0xA5, sz);
-  memcpy(v.blk + a, src, len);
-  v.addr = (uint64_t)(uintptr_t)v.blk + a;
-  return v;
-}
-
-uint32_t load_dword(const yu::IovSlot &S, uint32_t cr, uint32_t lim) {
-  if (cr >= ((lim + 3u) & ~3u)) return 0;
-  uint32_t x;
-  memcpy(&x, (const void *)(uintptr_t)(S.base + cr), 4);
-  return x;
-}
-
-// The destination block and the stores made into it.
-struct Store {
-  uint8_t *blk;
-  size_t total;
-  std::vector<uint8_t> cnt;
-  bool bad = false;  // outside the block, or misaligned
-  void put(uint64_t a, uint8_t v) {
-    const uint64_t i = a - (uint64_t)(uintptr_t)blk;
-    if (i >= total) {
-      bad = true;
-      return;
-    }
-    blk[i] = v;
-    if (cnt[i] < 255) ++cnt[i];
-  }
-  void b8(uint64_t a, uint8_t v) { put(a, v); }
-  void b16(uint64_t a, uint16_t v) {
-    if (a & 1u) bad = true;
-    put(a, (uint8_t)v);
-    put(a + 1, (uint8_t)(v >> 8));
-  }
-  void b32(uint64_t a, uint32_t v) {
-    if (a & 3u) bad = true;
-    for (int k = 0; k < 4; ++k) put(a + k, (uint8_t)(v >> (8 * k)));
-  }
-  void b128(uint64_t a, uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
-    b32(a, x);
-    b32(a + 4, y);
-    b32(a + 8, z);
-    b32(a + 12, w);
-  }
-};
 
 // One packet as k_pack<4, *, FILL> handles it: its value; the copy goes through st.
 // dst: the call's dst pointer; (o0, o1, oN): dst_offsets[i], [i + 1], [n].
@@ -188,23 +115,6 @@ uint32_t kernel_pack(Store &st, const std::vector<View> &views, int mode, bool f
     yu::iov_pack_field_store(st, fa0, fa1, put ? r >> 8 : fb0, put ? r & 0xFFu : fb1);
   }
   return r;
-}
-
-uint32_t scalar_value(const uint8_t *pkt, uint32_t len, int mode, bool have_addrs, const uint8_t *rec,
-                      uint16_t initial) {
-  if (mode == YU_MODE_RAW) return yu_checksum(pkt, len, initial);
-  std::vector<uint8_t> z(pkt, pkt + len);
-  const uint32_t f = yu::iov_mode_field(mode);
-  if (yu::iov_mode_tx(mode) && len >= f + 2u) z[f] = z[f + 1] = 0;
-  uint16_t x = 0;
-  if (mode != YU_MODE_ICMP) {
-    const uint32_t proto = (mode == YU_MODE_TCP || mode == YU_MODE_VERIFY_TCP) ? 6 : 17;
-    x = have_addrs ? yu_pseudo_header_checksum(proto, rec, 4, rec + 4, 4) : initial;
-    const uint8_t lb[2] = {(uint8_t)(len >> 8), (uint8_t)len};
-    x = yu_checksum(lb, 2, x);
-  }
-  x = yu_checksum(z.data(), len, x);
-  return yu::iov_mode_tx(mode) ? (uint16_t)~x : x;
 }
 
 const int kModes[6] = {YU_MODE_RAW, YU_MODE_UDP, YU_MODE_TCP, YU_MODE_ICMP, YU_MODE_VERIFY_TCP,
@@ -419,7 +329,5 @@ int main() {
     free(views[0].blk);
     free(views[1].blk);
   }
-  if (fails) return 1;
-  printf("%llu packets ok\n", (unsigned long long)checks);
-  return 0;
+  return finish();
 }

@@ -22,86 +22,13 @@
 // slot seam; 70 empty or one-byte views before the header; room one byte short,
 // room 0, decreasing offsets, a span cut by dst_offsets[n], and a view over
 // 65535 bytes.
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <random>
-#include <vector>
-
-#include "yucsum.h"
-#include "yucsum_iov.h"
+#include "iov_model.h"
 #include "yucsum_iov_pack.h"
 
 namespace {
 
 constexpr int kU = 4;
 constexpr size_t kCanary = 32;
-int fails = 0;
-uint64_t checks = 0;
-
-struct View {
-  uint8_t *blk;
-  uint64_t addr;
-  uint64_t len;
-};
-
-View place(const uint8_t *src, uint32_t len, uint32_t a) {
-  View v;
-  v.len = len;
-  if (len == 0) {
-    v.blk = nullptr;
-    v.addr = a ? 0x1000u + a : 0;  // never dereferenced
-    return v;
-  }
-  const size_t sz = (a + len + 3u) & ~(size_t)3;
-  v.blk = (uint8_t *)malloc(sz);
-  memset(v.blk, 0xA5, sz);
-  memcpy(v.blk + a, src, len);
-  v.addr = (uint64_t)(uintptr_t)v.blk + a;
-  return v;
-}
-
-uint32_t load_dword(const yu::IovSlot &S, uint32_t cr, uint32_t lim) {
-  if (cr >= ((lim + 3u) & ~3u)) return 0;
-  uint32_t x;
-  memcpy(&x, (const void *)(uintptr_t)(S.base + cr), 4);
-  return x;
-}
-
-// The destination block and the stores made into it.
-struct Store {
-  uint8_t *blk;
-  size_t total;
-  std::vector<uint8_t> cnt;
-  bool bad = false;  // outside the block, or misaligned
-  void put(uint64_t a, uint8_t v) {
-    const uint64_t i = a - (uint64_t)(uintptr_t)blk;
-    if (i >= total) {
-      bad = true;
-      return;
-    }
-    blk[i] = v;
-    if (cnt[i] < 255) ++cnt[i];
-  }
-  void b8(uint64_t a, uint8_t v) { put(a, v); }
-  void b16(uint64_t a, uint16_t v) {
-    if (a & 1u) bad = true;
-    put(a, (uint8_t)v);
-    put(a + 1, (uint8_t)(v >> 8));
-  }
-  void b32(uint64_t a, uint32_t v) {
-    if (a & 3u) bad = true;
-    for (int k = 0; k < 4; ++k) put(a + k, (uint8_t)(v >> (8 * k)));
-  }
-  void b128(uint64_t a, uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
-    b32(a, x);
-    b32(a + 4, y);
-    b32(a + 8, z);
-    b32(a + 12, w);
-  }
-};
 
 // One packet as k_pack_dg<4, *, FILL> handles it: its results; the copy goes
 // through st. dst: the call's dst pointer; (o0, o1, oN): dst_offsets[i], [i + 1], [n].
@@ -214,74 +141,6 @@ void kernel_pack_dg(Store &st, const std::vector<View> &views, int mode, bool fi
   if (fill) yu::iov_pack_dg_finish(st, Dd, len, D.f, !bad && st0, !bad && st1, r[0], r[1], hb[10], hb[11], fb0, fb1);
 }
 
-// The byte-wise composition over the concatenated bytes (include/yucsum.h: the
-// modes' definitions; the fill rule of yu_csum_fill_ragged). field[k]: the packet
-// offset of field k's first byte, -1 when it is not stored.
-void scalar_value(const uint8_t *p, uint32_t len, int mode, uint32_t r[2], int field[2]) {
-  r[0] = r[1] = 0;
-  field[0] = field[1] = -1;
-  const uint32_t hl = len ? (p[0] & 15u) * 4u : 0u;
-  if (mode == YU_MODE_VERIFY_IPV4) {
-    r[0] = yu_checksum(p, hl < len ? hl : len, 0);
-    return;
-  }
-  if (mode == YU_MODE_IPV4) {
-    uint8_t h[64] = {0};
-    const uint32_t cp = len < 64u ? len : 64u;
-    memcpy(h, p, cp);
-    if (cp >= 12) h[10] = h[11] = 0;
-    r[0] = (uint16_t)~yu_checksum(h, hl < cp ? hl : cp, 0);
-    if ((hl < len ? hl : len) >= 12) field[0] = 10;
-    return;
-  }
-  const uint32_t tl = len >= 4 ? ((uint32_t)p[2] << 8) | p[3] : 0u;
-  const bool valid = len >= 20 && hl <= tl && tl <= len;
-  if (mode == YU_MODE_VERIFY_RX) {
-    if (!valid) {
-      r[0] = YU_RX_INVALID;
-      return;
-    }
-    const uint16_t x = yu_checksum(p, hl, 0);
-    if (x == 0 || x == 0xFFFF) r[0] |= YU_RX_IP_OK;
-    const uint32_t proto = p[9], sl = tl - hl;
-    if (proto == 6 || proto == 17 || proto == 1) {
-      r[0] |= YU_RX_L4;
-      uint16_t xs = 0;
-      if (proto != 1) {
-        xs = yu_pseudo_header_checksum(proto, p + 12, 4, p + 16, 4);
-        const uint8_t lb[2] = {(uint8_t)(sl >> 8), (uint8_t)sl};
-        xs = yu_checksum(lb, 2, xs);
-      }
-      xs = yu_checksum(p + hl, sl, xs);
-      if (xs == 0 || xs == 0xFFFF) r[0] |= YU_RX_L4_OK;
-    }
-    return;
-  }
-  // TX_DATAGRAM
-  if (!valid || hl < 20) return;
-  {
-    uint8_t h[64] = {0};
-    memcpy(h, p, hl);
-    h[10] = h[11] = 0;
-    r[0] = (uint16_t)~yu_checksum(h, hl, 0);
-    field[0] = 10;
-  }
-  const uint32_t proto = p[9], sl = tl - hl;
-  const uint32_t fo = proto == 17 ? 6u : (proto == 6 ? 16u : (proto == 1 ? 2u : 0u));
-  const uint32_t mn = proto == 17 ? 8u : (proto == 6 ? 20u : 4u);
-  if (!fo || sl < mn) return;
-  std::vector<uint8_t> z(p + hl, p + tl);
-  z[fo] = z[fo + 1] = 0;
-  uint16_t xs = 0;
-  if (proto != 1) {
-    xs = yu_pseudo_header_checksum(proto, p + 12, 4, p + 16, 4);
-    const uint8_t lb[2] = {(uint8_t)(sl >> 8), (uint8_t)sl};
-    xs = yu_checksum(lb, 2, xs);
-  }
-  r[1] = (uint16_t)~yu_checksum(z.data(), sl, xs);
-  field[1] = (int)(hl + fo);
-}
-
 const int kModes[4] = {YU_MODE_IPV4, YU_MODE_VERIFY_IPV4, YU_MODE_VERIFY_RX, YU_MODE_TX_DATAGRAM};
 bool mode_fills(int m) { return m == YU_MODE_IPV4 || m == YU_MODE_TX_DATAGRAM; }
 
@@ -363,17 +222,6 @@ void check(const uint8_t *pkt, uint32_t len, const uint32_t *cut, int nv, uint32
   for (int i = 0; i < nv; ++i) views.push_back(place(pkt + cut[i], cut[i + 1] - cut[i], (aligns >> (2 * i)) & 3u));
   run(pkt, len, views, c, "mismatch");
   for (auto &v : views) free(v.blk);
-}
-
-// A datagram of len bytes: payload kind 0 random, 1 all 0x00, 2 all 0xFF, then
-// the header fields where the packet holds them.
-std::vector<uint8_t> datagram(std::mt19937_64 &rng, uint32_t len, int kind, uint32_t ihl, uint32_t tl, uint32_t proto) {
-  std::vector<uint8_t> p(len + 1);
-  for (auto &x : p) x = kind == 0 ? (uint8_t)rng() : (kind == 1 ? 0x00 : 0xFF);
-  if (len > 0) p[0] = (uint8_t)(0x40u | ihl);
-  if (len > 3) p[2] = (uint8_t)(tl >> 8), p[3] = (uint8_t)tl;
-  if (len > 9) p[9] = (uint8_t)proto;
-  return p;
 }
 
 void sort3(uint32_t *c) {
@@ -564,7 +412,5 @@ int main() {
     free(views[0].blk);
     free(views[1].blk);
   }
-  if (fails) return 1;
-  printf("%llu packets ok\n", (unsigned long long)checks);
-  return 0;
+  return finish();
 }

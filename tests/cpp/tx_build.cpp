@@ -20,65 +20,14 @@
 // device test's contract batch (T = 65535, T = 65536, room short by 3,
 // decreasing dst_offsets, doff 24 with L = 2), a span cut by dst_offsets[n] and
 // payload offsets that decrease or pass pay_offsets[n].
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <random>
-#include <vector>
-
-#include "yucsum.h"
+#include "iov_model.h"
 #include "yucsum_build.h"
-#include "yucsum_iov.h"
 #include "yucsum_iov_pack.h"
 
 namespace {
 
 constexpr int kU = 4;
 constexpr size_t kCanary = 48;
-int fails = 0;
-uint64_t checks = 0;
-
-uint32_t load_dword(const yu::IovSlot &S, uint32_t cr, uint32_t lim) {
-  if (cr >= ((lim + 3u) & ~3u)) return 0;
-  uint32_t x;
-  memcpy(&x, (const void *)(uintptr_t)(S.base + cr), 4);
-  return x;
-}
-
-// The destination block and the stores made into it.
-struct Store {
-  uint8_t *blk;
-  size_t total;
-  std::vector<uint8_t> cnt;
-  bool bad = false;  // outside the block, or misaligned
-  void put(uint64_t a, uint8_t v) {
-    const uint64_t i = a - (uint64_t)(uintptr_t)blk;
-    if (i >= total) {
-      bad = true;
-      return;
-    }
-    blk[i] = v;
-    if (cnt[i] < 255) ++cnt[i];
-  }
-  void b8(uint64_t a, uint8_t v) { put(a, v); }
-  void b16(uint64_t a, uint16_t v) {
-    if (a & 1u) bad = true;
-    put(a, (uint8_t)v);
-    put(a + 1, (uint8_t)(v >> 8));
-  }
-  void b32(uint64_t a, uint32_t v) {
-    if (a & 3u) bad = true;
-    for (int k = 0; k < 4; ++k) put(a + k, (uint8_t)(v >> (8 * k)));
-  }
-  void b128(uint64_t a, uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
-    b32(a, x);
-    b32(a + 4, y);
-    b32(a + 8, z);
-    b32(a + 12, w);
-  }
-};
 
 struct Result {
   uint32_t ipsum, xsum;  // as computed (the kernel stores {0, 0} to out when !ok)
@@ -399,7 +348,5 @@ int main() {
         for (uint32_t L : {1459u, 1460u, 1461u, 4099u, 9000u}) run(tcp, pay.data(), L, c, "long");
       }
   }
-  if (fails) return 1;
-  printf("%llu packets ok\n", (unsigned long long)checks);
-  return 0;
+  return finish();
 }

@@ -577,7 +577,7 @@ _call_shapes_and_poles()
 
 
 # ---------------------------------------------------------------------------
-# Layout "I": k_iov<4> / k_iov<4,fill>, the scatter-gather device calls (yu::plan_iov: a
+# Layout "I": k_iov<4> / k_iov<4,fill>, the scatter-gather device calls (yu::plan_wave: a
 # wave per packet at every count, the policy slot YU_NT's, else 2). A packet is a list of
 # (pool, alignment mod 16, length) views, the form of iov_layout.general_layout; the child
 # builds the yu_iovec table and first_iov by hand. Under the default set and the RUNS0 trio.

@@ -1,7 +1,7 @@
 """The whole-datagram scatter-gather device calls at the C-ABI boundary (include/yucsum.h,
 yu_csum_batch_iov_datagram / yu_csum_fill_iov_datagram / yu_iov_datagram_variant_n):
 exported and declared, every documented YU_EINVAL returned before any device work, the
-kernels yu::plan_iov names for the four datagram modes, and unchanged rows for the six
+kernels yu::plan_wave names for the four datagram modes, and unchanged rows for the six
 whole-packet modes. CPU only: no call here reaches a device (the arguments are refused
 first, or there is no device)."""
 import ctypes
@@ -12,10 +12,10 @@ import subprocess
 import pytest
 import torch
 
+import wave_plan
 from yustack_amd import _lib, batch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "yustack_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "yucsum.h")
 NAMES = ("yu_csum_batch_iov_datagram", "yu_csum_fill_iov_datagram", "yu_iov_datagram_variant_n")
 RAW, UDP, TCP, IPV4, ICMP, VERIFY_IPV4, VERIFY_TCP, VERIFY_UDP, VERIFY_RX, TX_DATAGRAM = range(10)
@@ -130,23 +130,8 @@ def test_python_front_end_refuses_before_the_library():
 
 
 @pytest.fixture(scope="module")
-def iov_plan(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("iov_plan_dg") / "iov_plan")
-    r = subprocess.run(["g++", "-O2", "-std=c++17", f"-I{ROOT}/include", "-D__HIP_PLATFORM_AMD__",
-                        "-I/opt/rocm/include", f"-I{CSRC}", os.path.join(ROOT, "tests", "cpp", "iov_plan.cpp"),
-                        os.path.join(CSRC, "yucsum_plan.cpp"), "-o", exe],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-
-    def run(cases, env=None):
-        args = [str(x) for c in cases for x in c]
-        e = {k: v for k, v in os.environ.items() if not k.startswith("YU_")}
-        e.update(env or {})
-        r = subprocess.run([exe, *args], capture_output=True, text=True, timeout=60, env=e)
-        assert r.returncode == 0, r.stderr[-2000:]
-        rows = [line.split(maxsplit=3) for line in r.stdout.splitlines()]
-        return [(int(k), int(pol), int(blocks), name) for k, pol, blocks, name in rows]
-    return run
+def iov_plan():
+    return lambda cases, env=None: wave_plan.plans("iov", cases, env)
 
 
 def test_plan_iov_names_the_datagram_kernels(iov_plan):

@@ -1,7 +1,7 @@
 """The packing scatter-gather device calls at the C-ABI boundary (include/yucsum.h,
 yu_csum_pack_iov / yu_csum_pack_fill_iov / yu_iov_pack_variant_n): exported and
 declared, every documented YU_EINVAL returned before any device work, the kernels
-yu::plan_iov_pack names, unchanged plan_iov rows, and what the Python front end
+yu::plan_wave names, unchanged rows for the in-place calls, and what the Python front end
 refuses. CPU only: no call here reaches a device (the arguments are refused first,
 or there is no device)."""
 import ctypes
@@ -12,10 +12,10 @@ import subprocess
 import pytest
 import torch
 
+import wave_plan
 from yustack_amd import _lib, batch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "yustack_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "yucsum.h")
 NAMES = ("yu_csum_pack_iov", "yu_csum_pack_fill_iov", "yu_iov_pack_variant_n")
 RAW, UDP, TCP, IPV4, ICMP, VERIFY_IPV4, VERIFY_TCP, VERIFY_UDP, VERIFY_RX, TX_DATAGRAM = range(10)
@@ -147,27 +147,8 @@ def test_python_front_end_refuses_before_the_library():
 
 
 @pytest.fixture(scope="module")
-def pack_plan(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("iov_pack_plan") / "iov_pack_plan")
-    r = subprocess.run(["g++", "-O2", "-std=c++17", f"-I{ROOT}/include", "-D__HIP_PLATFORM_AMD__",
-                        "-I/opt/rocm/include", f"-I{CSRC}", os.path.join(ROOT, "tests", "cpp", "iov_pack_plan.cpp"),
-                        os.path.join(CSRC, "yucsum_plan.cpp"), "-o", exe],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-
-    def run(cases, env=None):
-        args = [str(x) for c in cases for x in c]
-        e = {k: v for k, v in os.environ.items() if not k.startswith("YU_")}
-        e.update(env or {})
-        r = subprocess.run([exe, *args], capture_output=True, text=True, timeout=60, env=e)
-        assert r.returncode == 0, r.stderr[-2000:]
-        rows = []
-        for line in r.stdout.splitlines():
-            a, b = line.split(" | ")
-            rows.append(tuple((int(k), int(pol), int(blocks), name)
-                              for k, pol, blocks, name in (a.split(maxsplit=3), b.split(maxsplit=3))))
-        return rows
-    return run
+def pack_plan():
+    return wave_plan.pack_and_iov
 
 
 def test_plan_iov_pack_takes_plan_iovs_grid_and_leaves_its_rows(pack_plan):
@@ -175,7 +156,7 @@ def test_plan_iov_pack_takes_plan_iovs_grid_and_leaves_its_rows(pack_plan):
         for fill in ((0, 1) if m in FILL else (0,)):
             rows = pack_plan([(n, m, fill, cus) for n in (1, 4, 5, 4097, 1 << 20) for cus in (64, 256, 304)])
             for pack, iov in rows:
-                # plan_iov's rows for the whole-packet modes: kernel 0 / 1, policy 2, as before
+                # the in-place calls' rows for the whole-packet modes: kernel 0 / 1, policy 2, as before
                 assert iov[0] == fill and iov[1] == 2 and iov[3] == ("k_iov<4,fill>" if fill else "k_iov<4>")
                 assert pack[0] == 4 + fill and pack[3] == ("k_pack<4,fill>" if fill else "k_pack<4>")
                 assert pack[1:3] == iov[1:3]  # the same load policy and grid

@@ -11,31 +11,12 @@ slack 0 and 5, 70 one-byte views, and the out-of-contract rooms.
 The headers make no HIP call, so a plain g++ compiles the program; the same program
 (with its own main, run as that program only) also runs under AddressSanitizer +
 UBSan."""
-import os
-import subprocess
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = [os.path.join(ROOT, "tests", "cpp", "iov_pack.cpp"),
-           os.path.join(ROOT, "yustack_amd", "csrc", "yucsum_scalar.cpp")]
-INC = [f"-I{ROOT}/include", f"-I{ROOT}/yustack_amd/csrc"]
-
-
-def _build_and_run(tmp_path, name, flags, env=None):
-    exe = str(tmp_path / name)
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", *flags, *INC, *SOURCES, "-o", exe],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0 and r.stdout.strip().endswith("packets ok"), (r.stdout[-3000:], r.stderr[-3000:])
-    return int(r.stdout.split()[0])
+from cpp_program import build_and_run
 
 
 def test_iov_pack(tmp_path):
-    assert _build_and_run(tmp_path, "iov_pack", ["-O2"]) > 500000
+    assert build_and_run(tmp_path, "iov_pack") > 500000
 
 
 def test_iov_pack_under_sanitizers(tmp_path):
-    _build_and_run(tmp_path, "iov_pack_san",
-                   ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-fno-omit-frame-pointer"],
-                   env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    build_and_run(tmp_path, "iov_pack", sanitize=True)

@@ -2,7 +2,7 @@
 (include/yucsum.h, yu_csum_pack_iov_datagram / yu_csum_pack_fill_iov_datagram /
 yu_iov_pack_datagram_variant_n): exported and declared, every documented YU_EINVAL
 returned before any device work, YU_ENODEV without a device, the empty batch, the
-kernels yu::plan_iov_pack names for the four datagram modes (and the rows it keeps
+kernels yu::plan_wave names for the four datagram modes (and the rows it keeps
 for the others), and what the Python front end refuses. CPU only: no call here
 reaches a device (the arguments are refused first, or there is no device)."""
 import ctypes
@@ -13,10 +13,10 @@ import subprocess
 import pytest
 import torch
 
+import wave_plan
 from yustack_amd import _lib, batch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "yustack_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "yucsum.h")
 NAMES = ("yu_csum_pack_iov_datagram", "yu_csum_pack_fill_iov_datagram", "yu_iov_pack_datagram_variant_n")
 RAW, UDP, TCP, IPV4, ICMP, VERIFY_IPV4, VERIFY_TCP, VERIFY_UDP, VERIFY_RX, TX_DATAGRAM = range(10)
@@ -144,36 +144,14 @@ def test_python_front_end_refuses_before_the_library():
 
 
 @pytest.fixture(scope="module")
-def pack_plan(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("iov_pack_dg_plan") / "iov_pack_datagram_plan")
-    r = subprocess.run(["g++", "-O2", "-std=c++17", f"-I{ROOT}/include", "-D__HIP_PLATFORM_AMD__",
-                        "-I/opt/rocm/include", f"-I{CSRC}",
-                        os.path.join(ROOT, "tests", "cpp", "iov_pack_datagram_plan.cpp"),
-                        os.path.join(CSRC, "yucsum_plan.cpp"), "-o", exe],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-
-    def run(cases, env=None):
-        args = [str(x) for c in cases for x in c]
-        e = {k: v for k, v in os.environ.items() if not k.startswith("YU_")}
-        e.update(env or {})
-        r = subprocess.run([exe, *args], capture_output=True, text=True, timeout=60, env=e)
-        assert r.returncode == 0, r.stderr[-2000:]
-        rows, enum = [], None
-        for line in r.stdout.splitlines():
-            if line.startswith("enum "):
-                enum = [int(x) for x in line.split()[1:]]
-                continue
-            a, b = line.split(" | ")
-            rows.append(tuple((int(k), int(pol), int(blocks), name)
-                              for k, pol, blocks, name in (a.split(maxsplit=3), b.split(maxsplit=3))))
-        return rows, enum
-    return run
+def pack_plan():
+    return lambda cases, env=None: (wave_plan.pack_and_iov(cases, env), wave_plan.enum())
 
 
 def test_enum_values_keep_their_meaning(pack_plan):
     _, enum = pack_plan([])
-    assert enum == [0, 1, 2, 3, 4, 5, 6, 7, 8]
+    assert enum[:8] == [0, 1, 2, 3, 4, 5, 6, 7]
+    assert enum[8:] == [8, 9]  # k_build4, then the count
 
 
 def test_plan_rows_for_the_datagram_modes(pack_plan):
@@ -183,7 +161,7 @@ def test_plan_rows_for_the_datagram_modes(pack_plan):
             for pack, iov in rows:
                 assert iov[0] == 2 + fill and iov[1] == 2 and iov[3] == ("k_iov<4,dg,fill>" if fill else "k_iov<4,dg>")
                 assert pack[0] == 6 + fill and pack[3] == ("k_pack<4,dg,fill>" if fill else "k_pack<4,dg>")
-                assert pack[1:3] == iov[1:3]  # plan_iov's load policy and grid
+                assert pack[1:3] == iov[1:3]  # the in-place calls' load policy and grid
             assert [p[2] for p, _ in rows[-3:]] == [64 * 64, 256 * 64, 304 * 64]
             assert [p[2] for p, _ in rows[0:12:3]] == [1, 1, 2, 1025]  # a wave per packet, four per block
     # the whole-packet modes keep their rows

@@ -2,7 +2,7 @@
 case's written plan is the planner's at 64, 256 and 304 CUs, the built library names the
 same kernel, and the cases cover every key (kernel, form, policy, in place, layout) the
 planner can return (tests/cpp/plan_query.cpp --reachable; layout "I", the scatter-gather
-calls: tests/cpp/iov_plan.cpp under each knob set). Every kernel is also held in every
+calls: tests/cpp/wave_plan.cpp under each knob set). Every kernel is also held in every
 call shape (offset, null_out, ignored) and on the zero poles (pole_side, pole_data, all-zero
 and all-0xFF packets in place) its modes allow, and the child's comparisons are shown to
 fail on a wrong result and on a changed guard entry. tests/test_gpu_kernel_ledger.py runs
@@ -17,14 +17,13 @@ import numpy as np
 import pytest
 
 import kernel_cases as K
+import wave_plan
 from test_plan import CSRC, HIP_HEADERS, ROOT
 
 SOURCES = [os.path.join(ROOT, "tests", "cpp", "plan_query.cpp"), os.path.join(CSRC, "yucsum_plan.cpp")]
 HEADERS = [os.path.join(ROOT, "tests", "cpp", "plan_rows.h"), os.path.join(CSRC, "yucsum_plan.h"),
            os.path.join(CSRC, "yucsum_internal.h")]
 BIN = os.path.join(ROOT, "tests", "cpp", "build", "plan_query")
-IOV_BIN = os.path.join(ROOT, "tests", "cpp", "build", "iov_plan")
-IOV_SOURCES = [os.path.join(ROOT, "tests", "cpp", "iov_plan.cpp"), os.path.join(CSRC, "yucsum_plan.cpp")]
 KERNELS = 39  # the planner's; beside them the len(K.IOV_KERNELS) = 2 of the scatter-gather calls
 ALL_KERNELS = KERNELS + len(K.IOV_KERNELS)
 BASE_IDS = "6501eef667e93d86c2948da7fa59f9b79ce87323018151057e04abaa6b27f201"
@@ -43,26 +42,11 @@ def query():
 
 @pytest.fixture(scope="module")
 def iov_plan():
-    """tests/cpp/iov_plan.cpp, built as tests/test_iov_abi.py builds it; run(s, rows) asks
-    yu::plan_iov about (n, mode, fill, cus) rows under knob set s and returns (name, policy)."""
-    os.makedirs(os.path.dirname(IOV_BIN), exist_ok=True)
-    if not os.path.exists(IOV_BIN) or os.path.getmtime(IOV_BIN) < max(os.path.getmtime(p) for p in IOV_SOURCES + HEADERS):
-        r = subprocess.run(["g++", "-O2", "-std=c++17", f"-I{ROOT}/include", *HIP_HEADERS, *IOV_SOURCES, "-o", IOV_BIN],
-                           capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-3000:]
-
+    """run(s, rows) asks yu::plan_wave (tests/wave_plan.py) about the scatter-gather calls'
+    (n, mode, fill, cus) rows under knob set s and returns (name, policy)."""
     def run(s, rows):
-        env = {k: v for k, v in os.environ.items() if not k.startswith("YU_")}
-        if s:
-            env.update(K.KNOB_SETS[s], YU_TUNING="1")
-        out = []
-        for i in range(0, len(rows), 500):
-            r = subprocess.run([IOV_BIN, *[str(x) for row in rows[i:i + 500] for x in row]], capture_output=True,
-                               text=True, timeout=60, env=env)
-            assert r.returncode == 0, r.stderr[-2000:]
-            out += [(line.split(maxsplit=3)[3], line.split()[1]) for line in r.stdout.splitlines()]
-        assert len(out) == len(rows)
-        return out
+        env = dict(K.KNOB_SETS[s], YU_TUNING="1") if s else None
+        return [(name, str(policy)) for _, policy, _, name in wave_plan.plans("iov", rows, env)]
     return run
 
 
@@ -74,7 +58,7 @@ def reachable(query, iov_plan):
     keys = {ln[1:] for ln in lines if ln[0] == "K"}
     defaults = {ln[1:] for ln in lines if ln[0] == "D"}
     assert len(keys) > 200 and len(defaults) > 100 and len({k[0] for k in keys}) == KERNELS
-    # layout "I": what yu::plan_iov returns under each knob set
+    # layout "I": what yu::plan_wave returns under each knob set
     rows = [(n, K.MODES.index(m), f, cus) for m in K.IOV_MODES for f in ((0, 1) if m in K.FILL3 else (0,))
             for n in (1, 37, 4097, 1 << 20) for cus in (64, 256)]
     iov = set()
@@ -167,7 +151,7 @@ def test_cases_are_well_formed():
 def test_written_plans_are_the_planners(query, iov_plan):
     """Kernel, form and policy of every case under every set it runs in, at three CU
     counts (only `blocks` may differ between cards); ppw where the case states it. Layout
-    "I": yu::plan_iov's kernel and policy (a wave per packet: ppw 1)."""
+    "I": yu::plan_wave's kernel and policy (a wave per packet: ppw 1)."""
     text, want = [], []
     for s, env in enumerate(K.KNOB_SETS):
         text.append("# knobs: " + " ".join(f"{k}={v}" for k, v in env.items()))

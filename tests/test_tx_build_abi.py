@@ -1,7 +1,7 @@
 """The device-side sender at the C-ABI boundary (include/yucsum.h, yu_tx_build_ragged /
 yu_tx_build_variant_n / struct yu_tx_record): exported and declared, the record's
 layout, every documented YU_EINVAL returned before any device work, the empty batch,
-YU_ENODEV without a device, the kernel yu::plan_build names and its knobs behind the
+YU_ENODEV without a device, the kernel yu::plan_wave names and its knobs behind the
 gate, what the Python front end refuses and what packets.tx_records fills in. CPU only:
 no call here reaches a device (the arguments are refused first, or there is no device)."""
 import ctypes
@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import wave_plan
 from yustack_amd import _lib, batch, packets
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -113,28 +114,13 @@ def test_variant_name():
 
 
 @pytest.fixture(scope="module")
-def build_plan(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("tx_build_plan") / "tx_build_plan")
-    r = subprocess.run(["g++", "-O2", "-std=c++17", f"-I{ROOT}/include", "-D__HIP_PLATFORM_AMD__",
-                        "-I/opt/rocm/include", f"-I{CSRC}", os.path.join(ROOT, "tests", "cpp", "tx_build_plan.cpp"),
-                        os.path.join(CSRC, "yucsum_plan.cpp"), "-o", exe],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-
-    def run(cases, env=None):
-        args = [str(x) for c in cases for x in c]
-        e = {k: v for k, v in os.environ.items() if not k.startswith("YU_")}
-        e.update(env or {})
-        r = subprocess.run([exe, *args], capture_output=True, text=True, timeout=60, env=e)
-        assert r.returncode == 0, r.stderr[-2000:]
-        return [(int(k), int(pol), int(blocks), name)
-                for k, pol, blocks, name in (line.split(maxsplit=3) for line in r.stdout.splitlines())]
-    return run
+def build_plan():
+    return lambda cases, env=None: wave_plan.plans("build", [(n, 0, 0, cus) for n, cus in cases], env)
 
 
 def test_plan_rows(build_plan):
     rows = build_plan([(n, cus) for n in (1, 4, 5, 4097, 1 << 20) for cus in (64, 256, 304)])
-    assert all(r[0] == 0 and r[1] == 2 and r[3] == "k_build<4>" for r in rows)
+    assert all(r[0] == 8 and r[1] == 2 and r[3] == "k_build<4>" for r in rows)
     assert [r[2] for r in rows[-3:]] == [64 * 64, 256 * 64, 304 * 64]   # 64 blocks per CU
     assert [r[2] for r in rows[0:12:3]] == [1, 1, 2, 1025]              # a wave per packet, four per block
 
@@ -143,7 +129,7 @@ def test_plan_honours_the_knobs_behind_the_gate(build_plan):
     case = [(1 << 20, 256)]
     plain = build_plan(case)[0]
     assert build_plan(case, {"YU_NT": "0", "YU_BLOCKS_PER_CU": "1"})[0] == plain  # gate closed
-    assert build_plan(case, {"YU_TUNING": "1", "YU_NT": "0", "YU_BLOCKS_PER_CU": "1"})[0] == (0, 0, 256, "k_build<4>")
+    assert build_plan(case, {"YU_TUNING": "1", "YU_NT": "0", "YU_BLOCKS_PER_CU": "1"})[0] == (8, 0, 256, "k_build<4>")
 
 
 def test_python_front_end_refuses_before_the_library():

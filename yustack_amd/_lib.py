@@ -12,23 +12,50 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libyucsum.so")
 
-# Exported symbols declared in include/yucsum.h (checked by tests/test_abi.py).
-EXPORTS = (
-    "yu_checksum", "yu_checksum_combine", "yu_pseudo_header_checksum",
-    "yu_csum_batch_uniform", "yu_csum_batch_ragged",
-    "yu_csum_fill_uniform", "yu_csum_fill_ragged", "yu_csum_batch_iov", "yu_csum_fill_iov",
-    "yu_csum_batch_iov_datagram", "yu_csum_fill_iov_datagram", "yu_iov_datagram_variant_n",
-    "yu_csum_pack_iov", "yu_csum_pack_fill_iov", "yu_iov_pack_variant_n",
-    "yu_csum_pack_iov_datagram", "yu_csum_pack_fill_iov_datagram", "yu_iov_pack_datagram_variant_n",
-    "yu_tx_build_ragged", "yu_tx_build_variant_n",
-    "yu_csum_batch_host_uniform", "yu_csum_batch_host_ragged", "yu_csum_batch_host_iov",
-    "yu_csum_batch_host_uniform_multi", "yu_csum_batch_host_ragged_multi",
-    "yu_csum_batch_host_iov_multi",
-    "yu_csum_fill_host_uniform", "yu_csum_fill_host_ragged", "yu_csum_fill_host_iov",
-    "yu_abi_version", "yu_strerror", "yu_device_count", "yu_uniform_variant", "yu_uniform_variant_n",
-    "yu_ragged_variant", "yu_ragged_variant_n", "yu_ragged_fill_variant_n", "yu_iov_variant_n",
-    "yu_host_contexts", "yu_host_staging_bytes", "yu_host_staging_trim", "yu_hip_runtime_path",
-)
+_vp, _u16, _u32, _u64, _sz, _i32, _str = (ctypes.c_void_p, ctypes.c_uint16, ctypes.c_uint32, ctypes.c_uint64,
+                                          ctypes.c_size_t, ctypes.c_int, ctypes.c_char_p)
+# what the batch calls share: (data, stride, len, n | tables, n), mode, initial_arr, initial, addrs, out
+_UNIFORM = [_vp, _u64, _u32, _u64, _i32, _vp, _u16, _vp, _vp]
+_RAGGED = [_vp, _vp, _u64, _i32, _vp, _u16, _vp, _vp]
+
+
+def _same(names: str, restype, argtypes) -> dict:
+    return {name: (restype, argtypes) for name in names.split()}
+
+
+# Every exported symbol declared in include/yucsum.h: (restype, argtypes).
+PROTOTYPES = {
+    "yu_checksum": (_u16, [_vp, _sz, _u16]),
+    "yu_checksum_combine": (_u16, [_u16, _u16]),
+    "yu_pseudo_header_checksum": (_u16, [_u32, _vp, _sz, _vp, _sz]),
+    **_same("yu_csum_batch_uniform yu_csum_fill_uniform", _i32, _UNIFORM + [_vp]),  # + stream
+    **_same("yu_csum_batch_ragged yu_csum_fill_ragged yu_csum_batch_iov yu_csum_fill_iov", _i32, _RAGGED + [_vp]),
+    **_same("yu_csum_batch_iov_datagram yu_csum_fill_iov_datagram", _i32, [_vp, _vp, _u64, _i32, _vp, _vp]),
+    **_same("yu_csum_pack_iov yu_csum_pack_fill_iov", _i32, _RAGGED[:-1] + [_vp, _vp, _vp, _vp]),  # + dst, dst_offsets
+    **_same("yu_csum_pack_iov_datagram yu_csum_pack_fill_iov_datagram", _i32,
+            [_vp, _vp, _u64, _i32, _vp, _vp, _vp, _vp]),
+    "yu_tx_build_ragged": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    **_same("yu_csum_batch_host_uniform yu_csum_fill_host_uniform", _i32, _UNIFORM + [_i32]),  # + device
+    **_same("yu_csum_batch_host_ragged yu_csum_fill_host_ragged yu_csum_batch_host_iov yu_csum_fill_host_iov", _i32,
+            _RAGGED + [_i32]),
+    "yu_csum_batch_host_uniform_multi": (_i32, _UNIFORM + [_vp, _i32]),  # + devices, count
+    **_same("yu_csum_batch_host_ragged_multi yu_csum_batch_host_iov_multi", _i32, _RAGGED + [_vp, _i32]),
+    "yu_abi_version": (_i32, []),
+    "yu_strerror": (_str, [_i32]),
+    "yu_device_count": (_i32, []),
+    "yu_uniform_variant": (_str, [_u64, _u32, _i32, _u64]),
+    "yu_uniform_variant_n": (_str, [_u64, _u32, _u64, _i32, _u64]),
+    "yu_ragged_variant": (_str, [_i32]),
+    **_same("yu_ragged_variant_n yu_ragged_fill_variant_n", _str, [_i32, _u64]),
+    **_same("yu_iov_variant_n yu_iov_datagram_variant_n yu_iov_pack_variant_n yu_iov_pack_datagram_variant_n", _str,
+            [_i32, _u64, _i32]),
+    "yu_tx_build_variant_n": (_str, [_u64]),
+    "yu_host_contexts": (_i32, []),
+    "yu_host_staging_bytes": (_u64, [_i32, _vp]),
+    "yu_host_staging_trim": (_i32, [_i32]),
+    "yu_hip_runtime_path": (_str, []),
+}
+EXPORTS = tuple(PROTOTYPES)  # checked by tests/test_abi.py
 
 # Host-path staging bounds (include/yucsum.h): per context, between calls.
 HOST_SLICE_BYTES, HOST_SLICE_PACKETS = 32 << 20, 1 << 18
@@ -83,91 +110,10 @@ def lib() -> ctypes.CDLL:
     except Exception:  # noqa: BLE001 — any broken torch install: load without it
         pass
     L = ctypes.CDLL(LIB_PATH)
-    c = ctypes
-    L.yu_hip_runtime_path.restype = c.c_char_p
-    L.yu_hip_runtime_path.argtypes = []
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        f = getattr(L, name)
+        f.restype, f.argtypes = restype, argtypes
     check_runtime(L)
-    vp, u8, u16, u32, u64, sz, i32 = (c.c_void_p, c.c_uint8, c.c_uint16, c.c_uint32,
-                                      c.c_uint64, c.c_size_t, c.c_int)
-    L.yu_checksum.restype = u16
-    L.yu_checksum.argtypes = [vp, sz, u16]
-    L.yu_checksum_combine.restype = u16
-    L.yu_checksum_combine.argtypes = [u16, u16]
-    L.yu_pseudo_header_checksum.restype = u16
-    L.yu_pseudo_header_checksum.argtypes = [u32, vp, sz, vp, sz]
-    for name in ("yu_csum_batch_uniform", "yu_csum_fill_uniform"):
-        f = getattr(L, name)
-        f.restype = i32
-        f.argtypes = [vp, u64, u32, u64, i32, vp, u16, vp, vp, vp]
-    for name in ("yu_csum_batch_ragged", "yu_csum_fill_ragged", "yu_csum_batch_iov", "yu_csum_fill_iov"):
-        f = getattr(L, name)
-        f.restype = i32
-        f.argtypes = [vp, vp, u64, i32, vp, u16, vp, vp, vp]
-    L.yu_csum_batch_host_uniform.restype = i32
-    L.yu_csum_batch_host_uniform.argtypes = [vp, u64, u32, u64, i32, vp, u16, vp, vp, i32]
-    L.yu_csum_batch_host_ragged.restype = i32
-    L.yu_csum_batch_host_ragged.argtypes = [vp, vp, u64, i32, vp, u16, vp, vp, i32]
-    L.yu_csum_batch_host_iov.restype = i32
-    L.yu_csum_batch_host_iov.argtypes = [vp, vp, u64, i32, vp, u16, vp, vp, i32]
-    L.yu_csum_fill_host_uniform.restype = i32
-    L.yu_csum_fill_host_uniform.argtypes = [vp, u64, u32, u64, i32, vp, u16, vp, vp, i32]
-    L.yu_csum_fill_host_ragged.restype = i32
-    L.yu_csum_fill_host_ragged.argtypes = [vp, vp, u64, i32, vp, u16, vp, vp, i32]
-    L.yu_csum_fill_host_iov.restype = i32
-    L.yu_csum_fill_host_iov.argtypes = [vp, vp, u64, i32, vp, u16, vp, vp, i32]
-    L.yu_csum_batch_host_uniform_multi.restype = i32
-    L.yu_csum_batch_host_uniform_multi.argtypes = [vp, u64, u32, u64, i32, vp, u16, vp, vp, vp, i32]
-    L.yu_csum_batch_host_ragged_multi.restype = i32
-    L.yu_csum_batch_host_ragged_multi.argtypes = [vp, vp, u64, i32, vp, u16, vp, vp, vp, i32]
-    L.yu_csum_batch_host_iov_multi.restype = i32
-    L.yu_csum_batch_host_iov_multi.argtypes = [vp, vp, u64, i32, vp, u16, vp, vp, vp, i32]
-    L.yu_abi_version.restype = i32
-    L.yu_abi_version.argtypes = []
-    L.yu_strerror.restype = c.c_char_p
-    L.yu_strerror.argtypes = [i32]
-    L.yu_device_count.restype = i32
-    L.yu_device_count.argtypes = []
-    L.yu_uniform_variant.restype = c.c_char_p
-    L.yu_uniform_variant.argtypes = [u64, u32, i32, u64]
-    L.yu_uniform_variant_n.restype = c.c_char_p
-    L.yu_uniform_variant_n.argtypes = [u64, u32, u64, i32, u64]
-    L.yu_ragged_variant.restype = c.c_char_p
-    L.yu_ragged_variant.argtypes = [i32]
-    L.yu_ragged_variant_n.restype = c.c_char_p
-    L.yu_ragged_variant_n.argtypes = [i32, u64]
-    L.yu_ragged_fill_variant_n.restype = c.c_char_p
-    L.yu_ragged_fill_variant_n.argtypes = [i32, u64]
-    L.yu_iov_variant_n.restype = c.c_char_p
-    L.yu_iov_variant_n.argtypes = [i32, u64, i32]
-    for name in ("yu_csum_batch_iov_datagram", "yu_csum_fill_iov_datagram"):
-        f = getattr(L, name)
-        f.restype = i32
-        f.argtypes = [vp, vp, u64, i32, vp, vp]
-    L.yu_iov_datagram_variant_n.restype = c.c_char_p
-    L.yu_iov_datagram_variant_n.argtypes = [i32, u64, i32]
-    for name in ("yu_csum_pack_iov", "yu_csum_pack_fill_iov"):
-        f = getattr(L, name)
-        f.restype = i32
-        f.argtypes = [vp, vp, u64, i32, vp, u16, vp, vp, vp, vp, vp]
-    L.yu_iov_pack_variant_n.restype = c.c_char_p
-    L.yu_iov_pack_variant_n.argtypes = [i32, u64, i32]
-    for name in ("yu_csum_pack_iov_datagram", "yu_csum_pack_fill_iov_datagram"):
-        f = getattr(L, name)
-        f.restype = i32
-        f.argtypes = [vp, vp, u64, i32, vp, vp, vp, vp]
-    L.yu_iov_pack_datagram_variant_n.restype = c.c_char_p
-    L.yu_iov_pack_datagram_variant_n.argtypes = [i32, u64, i32]
-    L.yu_tx_build_ragged.restype = i32
-    L.yu_tx_build_ragged.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp]
-    L.yu_tx_build_variant_n.restype = c.c_char_p
-    L.yu_tx_build_variant_n.argtypes = [u64]
-    L.yu_host_contexts.restype = i32
-    L.yu_host_contexts.argtypes = []
-    L.yu_host_staging_bytes.restype = u64
-    L.yu_host_staging_bytes.argtypes = [i32, vp]
-    L.yu_host_staging_trim.restype = i32
-    L.yu_host_staging_trim.argtypes = [i32]
-    del u8
     _lib = L
     return L
 

@@ -76,6 +76,13 @@ def _opt(t, dtype, numel, device, name):
     return t
 
 
+def _result(out, count: int, device) -> torch.Tensor:
+    """The uint16 result tensor of ``count`` entries: ``out`` checked, or a new one."""
+    if out is None:
+        return torch.empty(max(count, 1), dtype=torch.uint16, device=device)[:count]
+    return _opt(out, torch.uint16, count, device, "out")
+
+
 def _ptr(t):
     return None if t is None else t.data_ptr()
 
@@ -102,11 +109,7 @@ def checksum_uniform(data: torch.Tensor, stride: int, length: int, n: int, mode=
     dev = data.device
     initial_arr = _opt(initial_arr, torch.uint16, n, dev, "initial_arr")
     addrs = _opt(addrs, torch.uint8, 8 * n, dev, "addrs")
-    k = outputs(m)
-    if out is None:
-        out = torch.empty(max(n * k, 1), dtype=torch.uint16, device=dev)[:n * k]
-    else:
-        _opt(out, torch.uint16, n * k, dev, "out")
+    out = _result(out, n * outputs(m), dev)
     with torch.cuda.device(dev):
         f = lib().yu_csum_fill_uniform if fill else lib().yu_csum_batch_uniform
         rc = f(data.data_ptr(), stride, length, n, m, _ptr(initial_arr), initial & 0xFFFF,
@@ -144,11 +147,7 @@ def checksum_ragged(data: torch.Tensor, offsets: torch.Tensor, mode="raw", *, in
     dev = data.device
     initial_arr = _opt(initial_arr, torch.uint16, n, dev, "initial_arr")
     addrs = _opt(addrs, torch.uint8, 8 * n, dev, "addrs")
-    k = outputs(m)
-    if out is None:
-        out = torch.empty(max(n * k, 1), dtype=torch.uint16, device=dev)[:n * k]
-    else:
-        _opt(out, torch.uint16, n * k, dev, "out")
+    out = _result(out, n * outputs(m), dev)
     with torch.cuda.device(dev):
         f = lib().yu_csum_fill_ragged if fill else lib().yu_csum_batch_ragged
         rc = f(data.data_ptr(), offsets.data_ptr(), n, m, _ptr(initial_arr), initial & 0xFFFF,
@@ -218,16 +217,62 @@ def _iov_table(pools, view_pool, view_off, view_len, first, validate: bool):
     return dev, table, fi, n
 
 
-def _iov_call(name: str, dev, table, fi, stream, call):
-    """Enqueues one scatter-gather call on ``stream`` (the table was built on the
-    current stream)."""
+IOV_DATAGRAM_MODES = (IPV4, VERIFY_IPV4, VERIFY_RX, TX_DATAGRAM)
+IOV_DATAGRAM_FILL_MODES = (IPV4, TX_DATAGRAM)
+
+
+def _iov_admit(who: str, m: int, datagram: bool, fill: bool) -> None:
+    """The modes a scatter-gather function takes: the whole-packet ones, or the
+    whole-datagram ones; with ``fill`` those of them that have a field to store."""
+    if datagram:
+        if m not in IOV_DATAGRAM_MODES:
+            raise ValueError(f"{who} takes ipv4, verify_ipv4, verify_rx and tx_datagram")
+        if fill and m not in IOV_DATAGRAM_FILL_MODES:
+            raise ValueError("fill=True takes ipv4 or tx_datagram")
+    else:
+        if m not in IOV_MODES:
+            raise ValueError(f"{who} takes the whole-packet modes: raw, udp, tcp, icmp, verify_tcp, verify_udp")
+        if fill and m not in IOV_FILL_MODES:
+            raise ValueError("fill=True takes udp, tcp or icmp")
+
+
+def _iov(who: str, datagram: bool, pack: bool, pools, view_pool, view_off, view_len, first, mode, *, initial=0,
+         initial_arr=None, addrs=None, dst=None, dst_offsets=None, out=None, stream=None, fill=False,
+         validate=True):
+    """The four scatter-gather functions: ``datagram`` picks the whole-datagram calls
+    (no side arrays), ``pack`` the packing ones (``dst``, ``dst_offsets``; returns the
+    triple). The call is enqueued on ``stream``; the table was built on the current one."""
+    m = _mode(mode)
+    _iov_admit(who, m, datagram, fill)
+    pools = list(pools)
+    dev, table, fi, n = _iov_table(pools, view_pool, view_off, view_len, first, validate)
+    initial_arr = _opt(initial_arr, torch.uint16, n, dev, "initial_arr")
+    addrs = _opt(addrs, torch.uint8, 8 * n, dev, "addrs")
+    if pack:
+        dst, do = _pack_dst(pools, dev, table, fi, n, dst, dst_offsets, validate)
+    out = _result(out, n * outputs(m), dev)
+    name = "yu_csum_" + (("pack_fill_" if fill else "pack_") if pack else ("fill_" if fill else "batch_")) + \
+        ("iov_datagram" if datagram else "iov")
+    args = [table.data_ptr(), fi.data_ptr(), n, m]
+    if not datagram:
+        args += [_ptr(initial_arr), initial & 0xFFFF, _ptr(addrs)]
+    if pack:
+        args += [dst.data_ptr(), do.data_ptr()]
     if stream is not None:
+        if pack:
+            do.record_stream(stream)
+            dst.record_stream(stream)
         stream.wait_stream(torch.cuda.current_stream(dev))
         table.record_stream(stream)
         fi.record_stream(stream)
     with torch.cuda.device(dev):
-        rc = call(getattr(lib(), name), _stream(dev, stream))
+        rc = getattr(lib(), name)(*args, out.data_ptr() if n else None, _stream(dev, stream))
     check(rc, name)
+    if not pack:
+        out.iov_table = (table, fi)
+        return out
+    out.iov_table = (table, fi, do)
+    return out, dst, (do if dst_offsets is None else dst_offsets)
 
 
 def checksum_iov(pools, view_pool: torch.Tensor, view_off: torch.Tensor, view_len: torch.Tensor,
@@ -252,27 +297,8 @@ def checksum_iov(pools, view_pool: torch.Tensor, view_off: torch.Tensor, view_le
     non-decreasing within the view count and that no packet is longer than 65535
     bytes (one small synchronisation). The returned tensor holds the table
     (``out.iov_table``), which must outlive the enqueued call."""
-    m = _mode(mode)
-    if m not in IOV_MODES:
-        raise ValueError("checksum_iov takes the whole-packet modes: raw, udp, tcp, icmp, verify_tcp, verify_udp")
-    if fill and m not in IOV_FILL_MODES:
-        raise ValueError("fill=True takes udp, tcp or icmp")
-    dev, table, fi, n = _iov_table(pools, view_pool, view_off, view_len, first, validate)
-    initial_arr = _opt(initial_arr, torch.uint16, n, dev, "initial_arr")
-    addrs = _opt(addrs, torch.uint8, 8 * n, dev, "addrs")
-    if out is None:
-        out = torch.empty(max(n, 1), dtype=torch.uint16, device=dev)[:n]
-    else:
-        _opt(out, torch.uint16, n, dev, "out")
-    _iov_call("yu_csum_fill_iov" if fill else "yu_csum_batch_iov", dev, table, fi, stream,
-              lambda f, s: f(table.data_ptr(), fi.data_ptr(), n, m, _ptr(initial_arr), initial & 0xFFFF,
-                             _ptr(addrs), out.data_ptr() if n else None, s))
-    out.iov_table = (table, fi)
-    return out
-
-
-IOV_DATAGRAM_MODES = (IPV4, VERIFY_IPV4, VERIFY_RX, TX_DATAGRAM)
-IOV_DATAGRAM_FILL_MODES = (IPV4, TX_DATAGRAM)
+    return _iov("checksum_iov", False, False, pools, view_pool, view_off, view_len, first, mode, initial=initial,
+                initial_arr=initial_arr, addrs=addrs, out=out, stream=stream, fill=fill, validate=validate)
 
 
 def checksum_iov_datagrams(pools, view_pool: torch.Tensor, view_off: torch.Tensor, view_len: torch.Tensor,
@@ -287,21 +313,8 @@ def checksum_iov_datagrams(pools, view_pool: torch.Tensor, view_off: torch.Tenso
     results, each what :func:`checksum_ragged` gives for the same bytes laid back to
     back. ``fill=True`` (IPV4, TX_DATAGRAM) also stores the fields
     :func:`checksum_ragged` stores, where they lie in the pools."""
-    m = _mode(mode)
-    if m not in IOV_DATAGRAM_MODES:
-        raise ValueError("checksum_iov_datagrams takes ipv4, verify_ipv4, verify_rx and tx_datagram")
-    if fill and m not in IOV_DATAGRAM_FILL_MODES:
-        raise ValueError("fill=True takes ipv4 or tx_datagram")
-    dev, table, fi, n = _iov_table(pools, view_pool, view_off, view_len, first, validate)
-    k = outputs(m)
-    if out is None:
-        out = torch.empty(max(n * k, 1), dtype=torch.uint16, device=dev)[:n * k]
-    else:
-        _opt(out, torch.uint16, n * k, dev, "out")
-    _iov_call("yu_csum_fill_iov_datagram" if fill else "yu_csum_batch_iov_datagram", dev, table, fi, stream,
-              lambda f, s: f(table.data_ptr(), fi.data_ptr(), n, m, out.data_ptr() if n else None, s))
-    out.iov_table = (table, fi)
-    return out
+    return _iov("checksum_iov_datagrams", True, False, pools, view_pool, view_off, view_len, first, mode, out=out,
+                stream=stream, fill=fill, validate=validate)
 
 
 def _overlaps(a: torch.Tensor, b: torch.Tensor) -> bool:
@@ -311,7 +324,7 @@ def _overlaps(a: torch.Tensor, b: torch.Tensor) -> bool:
     return a0 < b1 and b0 < a1
 
 
-def _pack_dst(pools, dev, table, fi, n, view_len, dst, dst_offsets, validate: bool):
+def _pack_dst(pools, dev, table, fi, n, dst, dst_offsets, validate: bool):
     """``dst`` and ``dst_offsets`` of the packing calls: the tight offsets and a new
     ``dst`` where they are not given, and the checks ``validate`` asks for. Returns
     (dst, the offsets as int64)."""
@@ -323,10 +336,9 @@ def _pack_dst(pools, dev, table, fi, n, view_len, dst, dst_offsets, validate: bo
             raise ValueError("dst overlaps a pool")
     need_len = dst_offsets is None or (validate and n > 0)
     if need_len:  # the packets' lengths: sums of their views' lengths
-        nviews = view_len.numel()
+        nviews = table.shape[0]  # a table of no views holds one view of no bytes
         ends = torch.zeros(nviews + 1, dtype=torch.int64, device=dev)
-        if nviews:
-            ends[1:] = torch.cumsum(table[:, 1].clamp(min=0), 0)
+        ends[1:] = torch.cumsum(table[:, 1].clamp(min=0), 0)
         f = fi.clamp(0, nviews)
         plen = (ends[f[1:]] - ends[f[:-1]]).clamp(min=0)
     if dst_offsets is None:
@@ -334,7 +346,7 @@ def _pack_dst(pools, dev, table, fi, n, view_len, dst, dst_offsets, validate: bo
         do[1:] = torch.cumsum(plen, 0)
     else:
         do = _dev_index(dst_offsets, "dst_offsets", dev, n + 1)
-        if do.dtype != torch.int64 or do.data_ptr() % 8:
+        if do.data_ptr() % 8:
             raise TypeError("dst_offsets must be 8-byte aligned")
     if dst is None:
         dst = torch.empty(max(int(do[-1].item()), 1), dtype=torch.uint8, device=dev)
@@ -374,28 +386,9 @@ def pack_iov(pools, view_pool: torch.Tensor, view_off: torch.Tensor, view_len: t
     on the device, that ``dst_offsets`` is non-decreasing, that every packet has
     room for its bytes and that ``dst_offsets[-1] <= dst.numel()``, and on the host
     that ``dst`` meets no pool. Slack bytes between packets are never written."""
-    m = _mode(mode)
-    if m not in IOV_MODES:
-        raise ValueError("pack_iov takes the whole-packet modes: raw, udp, tcp, icmp, verify_tcp, verify_udp")
-    if fill and m not in IOV_FILL_MODES:
-        raise ValueError("fill=True takes udp, tcp or icmp")
-    pools = list(pools)
-    dev, table, fi, n = _iov_table(pools, view_pool, view_off, view_len, first, validate)
-    initial_arr = _opt(initial_arr, torch.uint16, n, dev, "initial_arr")
-    addrs = _opt(addrs, torch.uint8, 8 * n, dev, "addrs")
-    dst, do = _pack_dst(pools, dev, table, fi, n, view_len, dst, dst_offsets, validate)
-    if out is None:
-        out = torch.empty(max(n, 1), dtype=torch.uint16, device=dev)[:n]
-    else:
-        _opt(out, torch.uint16, n, dev, "out")
-    if stream is not None:
-        do.record_stream(stream)
-        dst.record_stream(stream)
-    _iov_call("yu_csum_pack_fill_iov" if fill else "yu_csum_pack_iov", dev, table, fi, stream,
-              lambda f, s: f(table.data_ptr(), fi.data_ptr(), n, m, _ptr(initial_arr), initial & 0xFFFF,
-                             _ptr(addrs), dst.data_ptr(), do.data_ptr(), out.data_ptr() if n else None, s))
-    out.iov_table = (table, fi, do)
-    return out, dst, (do if dst_offsets is None else dst_offsets)
+    return _iov("pack_iov", False, True, pools, view_pool, view_off, view_len, first, mode, initial=initial,
+                initial_arr=initial_arr, addrs=addrs, dst=dst, dst_offsets=dst_offsets, out=out, stream=stream,
+                fill=fill, validate=validate)
 
 
 def pack_iov_datagrams(pools, view_pool: torch.Tensor, view_off: torch.Tensor, view_len: torch.Tensor,
@@ -412,27 +405,8 @@ def pack_iov_datagrams(pools, view_pool: torch.Tensor, view_off: torch.Tensor, v
     ``out`` is :func:`checksum_iov_datagrams`'s. ``fill=True`` (IPV4, TX_DATAGRAM) gives
     the copy the fields :func:`checksum_ragged` with ``fill=True`` would store on it;
     the pools are never written, so one header template may serve many packets."""
-    m = _mode(mode)
-    if m not in IOV_DATAGRAM_MODES:
-        raise ValueError("pack_iov_datagrams takes ipv4, verify_ipv4, verify_rx and tx_datagram")
-    if fill and m not in IOV_DATAGRAM_FILL_MODES:
-        raise ValueError("fill=True takes ipv4 or tx_datagram")
-    pools = list(pools)
-    dev, table, fi, n = _iov_table(pools, view_pool, view_off, view_len, first, validate)
-    dst, do = _pack_dst(pools, dev, table, fi, n, view_len, dst, dst_offsets, validate)
-    k = outputs(m)
-    if out is None:
-        out = torch.empty(max(n * k, 1), dtype=torch.uint16, device=dev)[:n * k]
-    else:
-        _opt(out, torch.uint16, n * k, dev, "out")
-    if stream is not None:
-        do.record_stream(stream)
-        dst.record_stream(stream)
-    _iov_call("yu_csum_pack_fill_iov_datagram" if fill else "yu_csum_pack_iov_datagram", dev, table, fi, stream,
-              lambda f, s: f(table.data_ptr(), fi.data_ptr(), n, m, dst.data_ptr(), do.data_ptr(),
-                             out.data_ptr() if n else None, s))
-    out.iov_table = (table, fi, do)
-    return out, dst, (do if dst_offsets is None else dst_offsets)
+    return _iov("pack_iov_datagrams", True, True, pools, view_pool, view_off, view_len, first, mode, dst=dst,
+                dst_offsets=dst_offsets, out=out, stream=stream, fill=fill, validate=validate)
 
 
 def build_datagrams(payload: torch.Tensor, pay_offsets: torch.Tensor, records: torch.Tensor, *,
@@ -507,10 +481,7 @@ def build_datagrams(payload: torch.Tensor, pay_offsets: torch.Tensor, records: t
             raise ValueError("a datagram has less room in dst than bytes")
         if not ok[4]:
             raise ValueError("a TCP record's doff is not 20..60, a multiple of 4 and within its payload")
-    if out is None:
-        out = torch.empty(max(2 * n, 1), dtype=torch.uint16, device=dev)[:2 * n]
-    else:
-        _opt(out, torch.uint16, 2 * n, dev, "out")
+    out = _result(out, 2 * n, dev)
     if stream is not None:
         stream.wait_stream(torch.cuda.current_stream(dev))
         for t in (po, do, dst, out):
@@ -523,33 +494,40 @@ def build_datagrams(payload: torch.Tensor, pay_offsets: torch.Tensor, records: t
     return dst, (do if dst_offsets is None else dst_offsets), out
 
 
+def _wave_variant(call: str, n: int, mode=None, fill: bool = False) -> str:
+    """What ``yu_<call>_variant_n`` names: (mode, n, fill) for the scatter-gather
+    calls, n alone for yu_tx_build_variant_n."""
+    args = (n,) if mode is None else (_mode(mode), n, 1 if fill else 0)
+    return getattr(lib(), f"yu_{call}_variant_n")(*args).decode()
+
+
 def build_variant(n: int = 1 << 20) -> str:
     """Name of the kernel :func:`build_datagrams` launches for a batch of n packets."""
-    return lib().yu_tx_build_variant_n(n).decode()
+    return _wave_variant("tx_build", n)
 
 
 def iov_pack_datagram_variant(mode="verify_rx", n: int = 1 << 20, fill: bool = False) -> str:
     """Name of the kernel the packing whole-datagram calls launch ("" for a mode
     they refuse)."""
-    return lib().yu_iov_pack_datagram_variant_n(_mode(mode), n, 1 if fill else 0).decode()
+    return _wave_variant("iov_pack_datagram", n, mode, fill)
 
 
 def iov_pack_variant(mode="raw", n: int = 1 << 20, fill: bool = False) -> str:
     """Name of the kernel the packing scatter-gather calls launch ("" for a mode
     they refuse)."""
-    return lib().yu_iov_pack_variant_n(_mode(mode), n, 1 if fill else 0).decode()
+    return _wave_variant("iov_pack", n, mode, fill)
 
 
 def iov_datagram_variant(mode="verify_rx", n: int = 1 << 20, fill: bool = False) -> str:
     """Name of the kernel the whole-datagram scatter-gather calls launch ("" for a
     mode they refuse)."""
-    return lib().yu_iov_datagram_variant_n(_mode(mode), n, 1 if fill else 0).decode()
+    return _wave_variant("iov_datagram", n, mode, fill)
 
 
 def iov_variant(mode="raw", n: int = 1 << 20, fill: bool = False) -> str:
     """Name of the kernel the scatter-gather device calls launch ("" for a mode
     they refuse)."""
-    return lib().yu_iov_variant_n(_mode(mode), n, 1 if fill else 0).decode()
+    return _wave_variant("iov", n, mode, fill)
 
 
 def _host_data(data, fill: bool):

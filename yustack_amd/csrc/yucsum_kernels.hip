@@ -71,19 +71,19 @@
 //   k_loop<U, BE> / k_loop_rx<U>: one wave per packet, for ragged bursts of up
 //     to 4096 packets and for few or sparse uniform packets > 4 KiB.
 //   k_iov<U, NT, FILL, DG>: scatter-gather packets (yu_csum_batch_iov / yu_csum_fill_iov,
-//     planned by yu::plan_iov): one wave per packet walking its views, each step U
+//     planned by yu::plan_wave): one wave per packet walking its views, each step U
 //     load slots of 1 KiB of whichever view comes next (yucsum_iov.h). DG: whole IPv4
 //     datagrams (yu_csum_batch_iov_datagram / yu_csum_fill_iov_datagram): the header
 //     gathered into the lanes a packet ahead, the walk windowed to [HL, TL).
 //   k_pack<U, NT, FILL>: the packing scatter-gather calls (yu_csum_pack_iov /
-//     yu_csum_pack_fill_iov, planned by yu::plan_iov_pack): k_iov's walk and sums,
+//     yu_csum_pack_fill_iov, planned by yu::plan_wave): k_iov's walk and sums,
 //     and every byte stored once at its place in one contiguous buffer
 //     (yucsum_iov_pack.h).
 //   k_pack_dg<U, NT, FILL>: the same for whole IPv4 datagrams
 //     (yu_csum_pack_iov_datagram / yu_csum_pack_fill_iov_datagram): k_iov's header
 //     gather, parse and epilogue, k_pack's store side over the plain walk, the window
 //     [HL, TL) applied to the sum alone.
-//   k_build<U, NT>: yu_tx_build_ragged (planned by yu::plan_build): one wave per
+//   k_build<U, NT>: yu_tx_build_ragged (planned by yu::plan_wave): one wave per
 //     outgoing datagram, the payload as a single view through k_pack's store side,
 //     the header encoded and summed from a 32-byte record and stored last
 //     (yucsum_build.h).
@@ -3485,24 +3485,42 @@ int batch_ragged(const uint8_t *data, uint8_t *fill, const uint64_t *offsets,
   return launch({true, 0, 0, 0, n, mode, fill != nullptr}, A, (hipStream_t)stream);
 }
 
-typedef void (*IovFn)(const yu_iovec *, const uint64_t *, const uint16_t *, const uint8_t *, IovArgs);
-const IovFn kIovFns[yu::kIovKernelCount][3] = {
-    {k_iov<4, 0, false>, k_iov<4, 1, false>, k_iov<4, 2, false>},
-    {k_iov<4, 0, true>, k_iov<4, 1, true>, k_iov<4, 2, true>},
-    {k_iov<4, 0, false, true>, k_iov<4, 1, false, true>, k_iov<4, 2, false, true>},
-    {k_iov<4, 0, true, true>, k_iov<4, 1, true, true>, k_iov<4, 2, true, true>},
+// The wave-per-packet kernels: one row per entry of YU_WAVE_KERNELS
+// (yucsum_plan.h), by load policy, from each family's template arguments. The
+// signatures differ (the packing forms add dst and dst_offsets, the datagram
+// packing form takes no side arrays, k_build its own tables), so a row fills the
+// member of its signature and leaves the others null.
+struct WaveFns {
+  void (*iov[3])(const yu_iovec *, const uint64_t *, const uint16_t *, const uint8_t *, IovArgs);
+  void (*pack[3])(const yu_iovec *, const uint64_t *, const uint16_t *, const uint8_t *, PackArgs);
+  void (*pack_dg[3])(const yu_iovec *, const uint64_t *, PackArgs);
+  void (*build[3])(const uint8_t *, const uint64_t *, const yu_tx_record *, BuildArgs);
 };
-// The packing form: the same tables, the packed copy besides (dst, dst_offsets).
-typedef void (*PackFn)(const yu_iovec *, const uint64_t *, const uint16_t *, const uint8_t *, PackArgs);
-const PackFn kPackFns[yu::k_pack4_dg - yu::k_pack4][3] = {
-    {k_pack<4, 0, false>, k_pack<4, 1, false>, k_pack<4, 2, false>},
-    {k_pack<4, 0, true>, k_pack<4, 1, true>, k_pack<4, 2, true>},
-};
-typedef void (*PackDgFn)(const yu_iovec *, const uint64_t *, PackArgs);
-const PackDgFn kPackDgFns[yu::kIovPackEnd - yu::k_pack4_dg][3] = {
-    {k_pack_dg<4, 0, false>, k_pack_dg<4, 1, false>, k_pack_dg<4, 2, false>},
-    {k_pack_dg<4, 0, true>, k_pack_dg<4, 1, true>, k_pack_dg<4, 2, true>},
-};
+#define YU_WFNS_Iov(U, FILL, DG) \
+  {{k_iov<U, 0, FILL, DG>, k_iov<U, 1, FILL, DG>, k_iov<U, 2, FILL, DG>}, {}, {}, {}}
+#define YU_WFNS_Pack_false(U, FILL) {{}, {k_pack<U, 0, FILL>, k_pack<U, 1, FILL>, k_pack<U, 2, FILL>}, {}, {}}
+#define YU_WFNS_Pack_true(U, FILL) \
+  {{}, {}, {k_pack_dg<U, 0, FILL>, k_pack_dg<U, 1, FILL>, k_pack_dg<U, 2, FILL>}, {}}
+#define YU_WFNS_Pack(U, FILL, DG) YU_WFNS_Pack_##DG(U, FILL)
+#define YU_WFNS_Build(U) {{}, {}, {}, {k_build<U, 0>, k_build<U, 1>, k_build<U, 2>}}
+#define YU_X(id, name, family, dg, fill, targs) YU_WFNS_##family targs,
+const WaveFns kWaveFns[] = {YU_WAVE_KERNELS(YU_X)};
+#undef YU_X
+static_assert(sizeof(kWaveFns) / sizeof(kWaveFns[0]) == yu::kWaveKernelCount, "one row per kernel");
+
+// A wave-per-packet launch: the device's plan, then the plan's kernel, taken from
+// the member `sig` of its row, with `args`.
+template <typename Fn, typename... Args>
+int launch_wave(Fn (WaveFns::*sig)[3], yu::WaveFamily family, uint64_t n, int mode, bool fill, void *stream,
+                Args... args) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return hip_status(e);
+  const yu::WavePlan p = yu::plan_wave(family, n, mode, fill, cu_count(dev), yu::env_knobs());
+  hipLaunchKernelGGL((kWaveFns[p.kernel].*sig)[p.policy], dim3(p.blocks), dim3(256), 0, (hipStream_t)stream,
+                     args...);
+  return hip_status(hipGetLastError());
+}
 
 // A scatter-gather device call. dg: the form for whole IPv4 datagrams, the modes
 // that parse headers out of the packet, which takes no side arrays (initial_arr,
@@ -3549,26 +3567,17 @@ int check_iov(const IovCall &c) {
 int call_iov(const IovCall &c) {
   const int rc = check_iov(c);
   if (rc != YU_OK || c.n == 0) return rc;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return hip_status(e);
-  const yu::IovPlan p = (c.pack ? yu::plan_iov_pack : yu::plan_iov)(c.n, c.mode, c.fill, cu_count(dev), yu::env_knobs());
-  const dim3 grid(p.blocks), block(256);
-  const hipStream_t stream = (hipStream_t)c.stream;
   if (!c.pack) {
     const IovArgs a = {c.out, c.n, c.initial, c.mode};
-    hipLaunchKernelGGL(kIovFns[p.kernel][p.policy], grid, block, 0, stream, c.views, c.first_iov, c.initial_arr,
-                       c.addrs, a);
-    return hip_status(hipGetLastError());
+    return launch_wave(&WaveFns::iov, yu::WaveFamily::Iov, c.n, c.mode, c.fill, c.stream, c.views, c.first_iov,
+                       c.initial_arr, c.addrs, a);
   }
   const PackArgs a = {c.out, c.dst, c.dst_offsets, c.n, c.initial, c.mode};
   if (c.dg)
-    hipLaunchKernelGGL(kPackDgFns[p.kernel - yu::k_pack4_dg][p.policy], grid, block, 0, stream, c.views,
+    return launch_wave(&WaveFns::pack_dg, yu::WaveFamily::Pack, c.n, c.mode, c.fill, c.stream, c.views,
                        c.first_iov, a);
-  else
-    hipLaunchKernelGGL(kPackFns[p.kernel - yu::k_pack4][p.policy], grid, block, 0, stream, c.views, c.first_iov,
-                       c.initial_arr, c.addrs, a);
-  return hip_status(hipGetLastError());
+  return launch_wave(&WaveFns::pack, yu::WaveFamily::Pack, c.n, c.mode, c.fill, c.stream, c.views, c.first_iov,
+                     c.initial_arr, c.addrs, a);
 }
 
 // The yu_iov*_variant_n calls: "" for a mode (or a fill) the form refuses.
@@ -3576,7 +3585,8 @@ const char *iov_variant(bool dg, bool pack, int mode, uint64_t n, int fill) {
   if (mode < 0 || mode >= YU_MODE_COUNT) return "";
   if (!(dg ? yu::iov_dg_mode_ok(mode) : yu::iov_mode_ok(mode))) return "";
   if (fill && !(dg ? yu::iov_dg_mode_tx(mode) : yu::iov_mode_tx(mode))) return "";
-  return (pack ? yu::plan_iov_pack : yu::plan_iov)(n, mode, fill != 0, 256, yu::env_knobs()).name;
+  const yu::WaveFamily family = pack ? yu::WaveFamily::Pack : yu::WaveFamily::Iov;
+  return yu::plan_wave(family, n, mode, fill != 0, 256, yu::env_knobs()).name;
 }
 
 // yu_tx_build_ragged: the record as the kernel reads it (eight little-endian
@@ -3598,11 +3608,6 @@ static_assert(offsetof(yu_tx_record, tos) == 28, "yu_tx_record.tos");
 static_assert(offsetof(yu_tx_record, reserved) == 29, "yu_tx_record.reserved");
 static_assert(offsetof(yu_tx_record, frag) == 30, "yu_tx_record.frag");
 
-typedef void (*BuildFn)(const uint8_t *, const uint64_t *, const yu_tx_record *, BuildArgs);
-const BuildFn kBuildFns[yu::kBuildKernelCount][3] = {
-    {k_build<4, 0>, k_build<4, 1>, k_build<4, 2>},
-};
-
 int tx_build(const uint8_t *payload, const uint64_t *pay_offsets, const yu_tx_record *recs, uint64_t n,
              uint8_t *dst, const uint64_t *dst_offsets, uint16_t *out, void *stream) {
   if (out && !aligned(out, 2)) return YU_EINVAL;  // EINVAL:side-align
@@ -3610,14 +3615,8 @@ int tx_build(const uint8_t *payload, const uint64_t *pay_offsets, const yu_tx_re
   if (!pay_offsets || !aligned(pay_offsets, 8) || !dst_offsets || !aligned(dst_offsets, 8) || !aligned(recs, 8))
     return YU_EINVAL;  // EINVAL:offsets
   if (!payload || !recs || !dst) return YU_EINVAL;  // EINVAL:data
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return hip_status(e);
-  const yu::BuildPlan p = yu::plan_build(n, cu_count(dev), yu::env_knobs());
   const BuildArgs a = {dst, dst_offsets, out, n};
-  hipLaunchKernelGGL(kBuildFns[p.kernel][p.policy], dim3(p.blocks), dim3(256), 0, (hipStream_t)stream, payload,
-                     pay_offsets, recs, a);
-  return hip_status(hipGetLastError());
+  return launch_wave(&WaveFns::build, yu::WaveFamily::Build, n, 0, false, stream, payload, pay_offsets, recs, a);
 }
 
 // Completion signal for the host path's direct mode (yucsum_internal.h):
@@ -3748,7 +3747,7 @@ int yu_tx_build_ragged(const uint8_t *payload, const uint64_t *pay_offsets, cons
 }
 
 const char *yu_tx_build_variant_n(uint64_t n) {
-  return yu::plan_build(n, 256, yu::env_knobs()).name;
+  return yu::plan_wave(yu::WaveFamily::Build, n, 0, false, 256, yu::env_knobs()).name;
 }
 
 const char *yu_uniform_variant(uint64_t stride, uint32_t len, int mode,

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "yucsum_internal.h"
+#include "yucsum_iov.h"
 
 namespace yu {
 
@@ -282,52 +283,32 @@ Plan plan(const Shape &s, int cus, const Knobs &k) {
   return p;
 }
 
-// k_iov: a wave per packet on the over-subscribed grid of the other
-// wave-per-packet kernels (64 blocks per CU, YU_BLOCKS_PER_CU overrides); the
-// load policy is YU_NT's, else slot 2. `mode` picks the kind: the whole-packet
-// sums share one kernel, the modes that parse an IPv4 header out of the packet
-// (IPV4, VERIFY_IPV4, VERIFY_RX, TX_DATAGRAM) the dg one; the grid is the same.
-IovPlan plan_iov(uint64_t n, int mode, bool fill, int cus, const Knobs &k) {
-  const bool dg = mode == YU_MODE_IPV4 || mode == YU_MODE_VERIFY_IPV4 || mode == YU_MODE_VERIFY_RX ||
-                  mode == YU_MODE_TX_DATAGRAM;
-  IovPlan p;
-  if (dg) {
-    p.kernel = fill ? k_iov4_dg_fill : k_iov4_dg;
-    p.name = fill ? "k_iov<4,dg,fill>" : "k_iov<4,dg>";
-  } else {
-    p.kernel = fill ? k_iov4_fill : k_iov4;
-    p.name = fill ? "k_iov<4,fill>" : "k_iov<4>";
-  }
-  p.policy = (uint8_t)(k.nt >= 0 ? k.nt : 2);
-  const uint64_t cap = (uint64_t)cus * (k.blocks_per_cu ? k.blocks_per_cu : 64u);
-  uint64_t blocks = (n + 3) / 4;  // 4 waves per block, a wave per packet
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  p.blocks = (uint32_t)blocks;
-  return p;
-}
-
-// k_pack: k_iov's grid and load policy (the source side is k_iov's), its own
-// kernels and names; the whole-datagram modes get k_pack's datagram kernels.
-IovPlan plan_iov_pack(uint64_t n, int mode, bool fill, int cus, const Knobs &k) {
-  IovPlan p = plan_iov(n, mode, fill, cus, k);
-  if (p.kernel == k_iov4_dg || p.kernel == k_iov4_dg_fill) {
-    p.kernel = fill ? k_pack4_dg_fill : k_pack4_dg;
-    p.name = fill ? "k_pack<4,dg,fill>" : "k_pack<4,dg>";
-  } else {
-    p.kernel = fill ? k_pack4_fill : k_pack4;
-    p.name = fill ? "k_pack<4,fill>" : "k_pack<4>";
-  }
-  return p;
-}
-
-// k_build: a wave per packet on the same over-subscribed grid (64 blocks per
-// CU, YU_BLOCKS_PER_CU overrides); the payload is read once, so the load policy
-// is k_iov's (YU_NT's, else slot 2).
-BuildPlan plan_build(uint64_t n, int cus, const Knobs &k) {
-  BuildPlan p;
-  p.kernel = k_build4;
-  p.name = "k_build<4>";
+// The wave-per-packet kernels: a wave per packet, four per block, on the over-
+// subscribed grid of the other wave-per-packet kernels (64 blocks per CU,
+// YU_BLOCKS_PER_CU overrides); the load policy is YU_NT's, else slot 2 (k_pack's
+// source side is k_iov's, and k_build reads its payload once). `mode` picks the
+// kind: the whole-packet sums share one kernel, the modes that parse an IPv4 header
+// out of the packet (IPV4, VERIFY_IPV4, VERIFY_RX, TX_DATAGRAM) take the dg one;
+// the grid is the same.
+WavePlan plan_wave(WaveFamily family, uint64_t n, int mode, bool fill, int cus, const Knobs &k) {
+  struct Row {
+    const char *name;
+    WaveFamily family;
+    bool dg, fill;
+  };
+  static constexpr Row rows[kWaveKernelCount] = {
+#define YU_X(id, name, family, dg, fill, targs) {name, WaveFamily::family, dg, fill},
+      YU_WAVE_KERNELS(YU_X)
+#undef YU_X
+  };
+  const bool build = family == WaveFamily::Build;
+  const bool dg = !build && iov_dg_mode_ok(mode);
+  fill = fill && !build;
+  int id = 0;  // every (family, dg, fill) a call can ask for has its row
+  while (rows[id].family != family || rows[id].dg != dg || rows[id].fill != fill) ++id;
+  WavePlan p;
+  p.kernel = (WaveKernel)id;
+  p.name = rows[id].name;
   p.policy = (uint8_t)(k.nt >= 0 ? k.nt : 2);
   const uint64_t cap = (uint64_t)cus * (k.blocks_per_cu ? k.blocks_per_cu : 64u);
   uint64_t blocks = (n + 3) / 4;  // 4 waves per block, a wave per packet

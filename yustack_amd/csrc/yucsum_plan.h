@@ -1,8 +1,11 @@
 // yucsum_plan.h — the launch plan: which kernel a batch gets, in which form, with
 // which load policy and on which grid. One list of kernels (YU_KERNELS) and one
 // pure function (plan) hold the whole decision; yucsum_kernels.hip builds its
-// function table from the same list and launches what the plan names. No HIP call
-// is made here, so tests/cpp/plan_table.cpp checks every decision on a CPU.
+// function table from the same list and launches what the plan names. The
+// wave-per-packet calls (scatter-gather, packing, yu_tx_build_ragged) have the
+// same pair beside it: YU_WAVE_KERNELS and plan_wave. No HIP call is made here,
+// so tests/cpp/plan_table.cpp and tests/cpp/wave_plan.cpp check every decision
+// on a CPU.
 #ifndef YUCSUM_PLAN_H
 #define YUCSUM_PLAN_H
 
@@ -173,43 +176,42 @@ struct Plan {
 
 Plan plan(const Shape &s, int cus, const Knobs &k);
 
-// The scatter-gather device calls (yu_csum_batch_iov / yu_csum_fill_iov) have a
-// plan of their own: one kernel family, k_iov (yucsum_iov.h), which is not one
-// of YU_KERNELS because no uniform or ragged batch ever takes it.
-enum IovKernel : uint8_t {
-  k_iov4, k_iov4_fill, k_iov4_dg, k_iov4_dg_fill, kIovKernelCount,
-  // k_pack (yucsum_iov_pack.h), the packing calls' family: rows of its own table
-  k_pack4 = kIovKernelCount, k_pack4_fill,
-  // k_pack_dg, the packing calls for whole IPv4 datagrams (named k_pack<4,dg>)
-  k_pack4_dg, k_pack4_dg_fill, kIovPackEnd
+// The wave-per-packet device calls have a list and a plan of their own: the
+// scatter-gather sums (k_iov, yucsum_iov.h), their packing form (k_pack, k_pack_dg:
+// yucsum_iov_pack.h) and yu_tx_build_ragged (k_build, yucsum_build.h). None is one
+// of YU_KERNELS, because no uniform or ragged batch ever takes them. Each once:
+// X(id, name, family, dg, fill, targs).
+//   dg     the kind for whole IPv4 datagrams (the modes of yu::iov_dg_mode_ok)
+//   fill   the instantiation that stores the checksum fields
+//   targs  what yucsum_kernels.hip instantiates the family's template with
+// The ids are the rows of yucsum_kernels.hip's function table, in this order.
+#define YU_WAVE_KERNELS(X)                                                          \
+  X(iov4, "k_iov<4>", Iov, false, false, (4, false, false))                         \
+  X(iov4_fill, "k_iov<4,fill>", Iov, false, true, (4, true, false))                 \
+  X(iov4_dg, "k_iov<4,dg>", Iov, true, false, (4, false, true))                     \
+  X(iov4_dg_fill, "k_iov<4,dg,fill>", Iov, true, true, (4, true, true))             \
+  X(pack4, "k_pack<4>", Pack, false, false, (4, false, false))                      \
+  X(pack4_fill, "k_pack<4,fill>", Pack, false, true, (4, true, false))              \
+  X(pack4_dg, "k_pack<4,dg>", Pack, true, false, (4, false, true))                  \
+  X(pack4_dg_fill, "k_pack<4,dg,fill>", Pack, true, true, (4, true, true))          \
+  X(build4, "k_build<4>", Build, false, false, (4))
+
+enum class WaveFamily : uint8_t { Iov, Pack, Build };
+enum WaveKernel : uint8_t {
+#define YU_X(id, ...) k_##id,
+  YU_WAVE_KERNELS(YU_X)
+#undef YU_X
+  kWaveKernelCount
 };
-constexpr int kIovPackKernelCount = kIovPackEnd - k_pack4;
-struct IovPlan {
-  IovKernel kernel;
+struct WavePlan {
+  WaveKernel kernel;
   uint8_t policy;  // load-policy slot: 0 plain, 1 nt, 2 plain for a step's first slot, nt for the rest
   uint32_t blocks;
-  const char *name;  // what yu_iov_variant_n / yu_iov_datagram_variant_n return
+  const char *name;  // what the yu_iov*_variant_n calls and yu_tx_build_variant_n return
 };
-// mode: one of the modes the form takes (yu::iov_mode_ok), or one of the whole-
-// datagram modes of yu_csum_batch_iov_datagram (yu::iov_dg_mode_ok): the dg kernels.
-IovPlan plan_iov(uint64_t n, int mode, bool fill, int cus, const Knobs &k);
-// The packing calls (yu_csum_pack_iov / yu_csum_pack_fill_iov): k_pack on
-// plan_iov's grid and load policy. mode: one yu::iov_mode_ok takes, or one of the
-// whole-datagram modes (yu_csum_pack_iov_datagram / yu_csum_pack_fill_iov_datagram):
-// the dg kernels.
-IovPlan plan_iov_pack(uint64_t n, int mode, bool fill, int cus, const Knobs &k);
-
-// yu_tx_build_ragged has a plan of its own too: one kernel, k_build
-// (yucsum_build.h), a wave per packet on k_iov's grid. Not one of YU_KERNELS:
-// no checksum batch ever takes it.
-enum BuildKernel : uint8_t { k_build4, kBuildKernelCount };
-struct BuildPlan {
-  BuildKernel kernel;
-  uint8_t policy;  // load-policy slot, as IovPlan's
-  uint32_t blocks;
-  const char *name;  // what yu_tx_build_variant_n returns
-};
-BuildPlan plan_build(uint64_t n, int cus, const Knobs &k);
+// Iov, Pack: any mode; one of the whole-datagram modes (yu::iov_dg_mode_ok) picks
+// the dg kernels, every other the whole-packet ones. Build: mode and fill are ignored.
+WavePlan plan_wave(WaveFamily family, uint64_t n, int mode, bool fill, int cus, const Knobs &k);
 
 }  // namespace yu
 #pragma GCC visibility pop
