@@ -73,7 +73,8 @@ extern "C" {
 /*                  parse headers out of the packet; the whole-datagram  */
 /*                  calls (yu_csum_*_iov_datagram) take those four and   */
 /*                  refuse every other mode.                             */
-/*  [out]           out == NULL in a yu_csum_batch_* call, or h_out ==   */
+/*  [out]           out == NULL in a yu_csum_batch_* call or in          */
+/*                  yu_rx_split_ragged, or h_out ==                      */
 /*                  NULL in a yu_csum_batch_host_* call, with n > 0 (the */
 /*                  fill calls take NULL: no result array; an empty     */
 /*                  batch, n == 0, is a no-op returning YU_OK).          */
@@ -84,13 +85,15 @@ extern "C" {
 /*                  yu_csum_fill_iov_datagram: VERIFY_IPV4, VERIFY_RX.   */
 /*  [side-align]    device calls: initial_arr not 2-byte aligned, addrs  */
 /*                  not 4-byte aligned, out not 2-byte aligned           */
-/*                  (yu_tx_build_ragged: out).                           */
+/*                  (yu_tx_build_ragged: out; yu_rx_split_ragged: out,   */
+/*                  and pay_len not 4-byte aligned).                     */
 /*  [data]          data == NULL with n > 0 (device calls), h_data ==    */
 /*                  NULL while the packets hold bytes (host calls), iov  */
 /*                  == NULL while first_iov names views; views == NULL  */
 /*                  with n > 0 (yu_csum_*_iov); dst == NULL with n > 0   */
 /*                  (yu_csum_pack_*_iov); payload, recs or dst == NULL   */
-/*                  with n > 0 (yu_tx_build_ragged).                     */
+/*                  with n > 0 (yu_tx_build_ragged); data, pay, recs or  */
+/*                  pay_len == NULL with n > 0 (yu_rx_split_ragged).     */
 /*  [len-transport] a packet of a mode other than RAW longer than        */
 /*                  YU_MAX_TRANSPORT_LEN (uniform len; every host ragged */
 /*                  or iov packet). Device ragged batches are not read   */
@@ -107,6 +110,8 @@ extern "C" {
 /*                  yu_csum_pack_*_iov: also dst_offsets == NULL or not  */
 /*                  8-byte aligned; yu_tx_build_ragged: pay_offsets or   */
 /*                  dst_offsets == NULL or not 8-byte aligned, recs not  */
+/*                  8-byte aligned; yu_rx_split_ragged: offsets or       */
+/*                  pay_offsets == NULL or not 8-byte aligned, recs not  */
 /*                  8-byte aligned.                                      */
 /*  [iov-view]    a view with base == NULL and len > 0.                */
 /*  [fill-align]    yu_csum_fill_uniform: data or stride not a multiple  */
@@ -274,6 +279,7 @@ uint16_t yu_pseudo_header_checksum(uint32_t protocol,
 #define YU_RX_L4 2u      /* transport (TCP/UDP/ICMP) present and checked */
 #define YU_RX_L4_OK 4u   /* transport checksum verifies */
 #define YU_RX_INVALID 8u /* IPv4.IsValid fails (nothing else is set) */
+#define YU_RX_SPLIT 16u  /* yu_rx_split_ragged only: record, pay_len and payload of this packet are defined */
 
 /* Packets handed to the transport/IPv4/ICMP modes must be <= 65535 bytes
  * (the IPv4 total-length limit; the reference's uint16 length arithmetic is
@@ -686,6 +692,92 @@ int yu_tx_build_ragged(const uint8_t *payload, const uint64_t *pay_offsets,
                        uint8_t *dst, const uint64_t *dst_offsets,
                        uint16_t *out, void *stream);
 
+/* Received IPv4 datagrams taken apart on the device: the inverse of
+ * yu_tx_build_ragged. After its checksums (YU_MODE_VERIFY_RX) the reference
+ * does four more things with a received datagram before the payload is queued:
+ * ipv4.HandlePacket (network/ipv4/ipv4.go:62-77) checks IsValid and trims the
+ * IPv4 header, Nic.DeliverTransportPacket (stack/nic.go:125-153) checks the
+ * transport header's minimum size and reads the ports, segment.parse
+ * (transport/tcp/segment.go:81-109) checks DataOffset, reads seq / ack / flags /
+ * window and trims the header, udp.endpoint.HandlePacket
+ * (transport/udp/endpoint.go:191-199) checks Length() and trims 8 bytes.
+ * yu_rx_split_ragged is that composition for a batch, in one pass over it: per
+ * packet VERIFY_RX's flags, the header fields as one yu_tx_record, and the
+ * payload stored contiguously.
+ *
+ * Call discipline: that of yu_tx_build_ragged, word for word. Every pointer is
+ * a DEVICE pointer; asynchronous on `stream`, no allocation, no
+ * synchronisation, graph-capturable, YU_ENODEV without a device, n == 0 a no-op
+ * returning YU_OK after the checks that do not need n.
+ *
+ * Input: the ragged batch yu_csum_batch_ragged takes, packet i =
+ * data[offsets[i], offsets[i+1]) (n + 1 DEVICE uint64 offsets, 8-byte aligned),
+ * at any byte alignment. `pay_offsets` holds n + 1 DEVICE uint64 values, 8-byte
+ * aligned, and gives packet i the span pay[pay_offsets[i], pay_offsets[i+1]);
+ * slack and room are yu_csum_pack_iov's dst_offsets rules. It may be the very
+ * array `offsets` (a room of the packet's length always suffices): the tables
+ * are only read. pay[0, pay_offsets[n]) overlaps nothing the call reads or
+ * writes elsewhere (not checked).
+ *
+ * Per packet, with b its bytes, len its length, HL = HeaderLength(), TL =
+ * TotalLength(), P = Protocol(), the segment S = b[HL:TL], slen = TL - HL and H
+ * yu_tx_build_ragged's transport header length (TCP 20, UDP 8, ICMP 4, any other
+ * protocol 0):
+ *
+ * out[i] is exactly the value yu_csum_batch_ragged(VERIFY_RX) gives the packet
+ * (YU_RX_IP_OK, _L4, _L4_OK, _INVALID), plus YU_RX_SPLIT, which is set iff
+ *   IsValid holds: len >= 20 && HL <= TL <= len;
+ *   HL >= 20 (the address bytes are header bytes);
+ *   slen >= H (stack/nic.go:133);
+ *   TCP: 20 <= DataOffset() <= slen (segment.go:94-97);
+ *   UDP: Length() <= slen (udp/endpoint.go:194).
+ * Checksum outcomes do not enter YU_RX_SPLIT: the reference does not drop on
+ * them (udp/endpoint.go:191-229), the caller combines the bits.
+ *
+ * With YU_RX_SPLIT, recs[i] holds the datagram's fields in yu_tx_record's
+ * layout and byte-order rules: src = b[12:16], dst = b[16:20], proto = P, ttl =
+ * b[8], ip_id = BE16(b[4:6]), tos = b[1], frag = BE16(b[6:8]), reserved = 0;
+ * TCP: sport, dport, seq, ack, window, flags = S[13], doff = DataOffset(); UDP:
+ * sport, dport (the TCP fields and doff are 0); ICMP: sport = type << 8 | code,
+ * everything else 0; any other protocol: no transport fields. Not carried: the
+ * IPv4 option bytes (HandlePacket trims them), TCP's urgent pointer, the low
+ * nibble of TCP byte 12, and UDP's Length() when it is below slen. pay_len[i] =
+ * L = slen - H, and the payload S[H:slen] is stored at pay[pay_offsets[i], +L).
+ * For TCP it starts with the doff - 20 option bytes, the form
+ * yu_tx_build_ragged takes it in. Bytes of b past TL are left out (VERIFY_RX's
+ * reading of Payload()).
+ * Without YU_RX_SPLIT, recs[i] is 32 zero bytes, pay_len[i] = 0 and no byte of
+ * pay is stored.
+ *
+ * Stores and reads: every record, every pay_len and every out is stored by the
+ * call (nothing needs pre-clearing). Every payload byte is stored by exactly one
+ * store, never a read-modify-write (with tight pay_offsets the rest of a dword
+ * belongs to another wave); slack, and anything outside pay[0, pay_offsets[n]),
+ * is never written. Reads lie in the dwords holding data[0, offsets[n]).
+ *
+ * Round trip: for a datagram with IHL 5, TL == len, YU_RX_SPLIT set, UDP
+ * Length() == slen, TCP urgent pointer 0 and data-offset low nibble 0, whose two
+ * checksum fields hold the values YU_MODE_TX_DATAGRAM defines,
+ * yu_tx_build_ragged over (pay, pay_offsets, recs) reproduces it byte for byte.
+ *
+ * Out of contract (the tables are device memory and are not read on the host):
+ * a packet at which offsets decreases, one longer than YU_MAX_TRANSPORT_LEN or
+ * one ending past offsets[n] gets four unspecified results, and unspecified
+ * bytes inside its own pay span only. A packet whose L exceeds its room in pay,
+ * or at which pay_offsets decreases, keeps exact out, recs and pay_len; only the
+ * bytes inside its own span [pay_offsets[i], min(pay_offsets[i+1],
+ * pay_offsets[n])) are unspecified. In both cases: never a fault or a hang,
+ * every other packet is exact, and nothing outside spans is written.
+ *
+ * YU_EINVAL (Preconditions above): [data]: data, pay, recs or pay_len NULL with
+ * n > 0; [out]: out NULL with n > 0; [offsets]: offsets or pay_offsets NULL or
+ * not 8-byte aligned, recs not 8-byte aligned; [side-align]: out not 2-byte
+ * aligned or pay_len not 4-byte aligned (checked without n). */
+int yu_rx_split_ragged(const uint8_t *data, const uint64_t *offsets, uint64_t n,
+                       uint8_t *pay, const uint64_t *pay_offsets,
+                       yu_tx_record *recs, uint32_t *pay_len,
+                       uint16_t *out, void *stream);
+
 /* Host-memory field writer: the matching yu_csum_batch_host_* call (TX modes
  * UDP/TCP/IPV4/ICMP/TX_DATAGRAM only), then each result stored big-endian into the
  * packet's checksum field in host memory, as the device writer does
@@ -827,6 +919,8 @@ const char *yu_iov_pack_datagram_variant_n(int mode, uint64_t n, int fill);
 /* The kernel variant yu_tx_build_ragged launches for a batch of n packets. No
  * device needed. */
 const char *yu_tx_build_variant_n(uint64_t n);
+/* The same for yu_rx_split_ragged. */
+const char *yu_rx_split_variant_n(uint64_t n);
 
 #ifdef __cplusplus
 }

@@ -3,7 +3,7 @@
 Thin Python front end over the C ABI's batched entry points
 (``yu_csum_batch_uniform`` / ``yu_csum_batch_ragged`` / ``yu_csum_batch_iov`` /
 ``yu_csum_batch_iov_datagram`` / ``yu_csum_pack_iov`` / ``yu_csum_pack_iov_datagram`` / ``yu_csum_fill_*`` /
-``yu_tx_build_ragged`` / ``yu_csum_batch_host_uniform``,
+``yu_tx_build_ragged`` / ``yu_rx_split_ragged`` / ``yu_csum_batch_host_uniform``,
 include/yucsum.h). PyTorch is used only for device
 memory and streams: the arithmetic happens in the hand-written gfx950 kernels of
 ``csrc/yucsum_kernels.hip``. There is no CPU fallback — without a HIP device every
@@ -41,6 +41,7 @@ MODES = {"raw": RAW, "udp": UDP, "tcp": TCP, "ipv4": IPV4, "icmp": ICMP,
          "verify_rx": VERIFY_RX, "tx_datagram": TX_DATAGRAM}
 # VERIFY_RX result bits (include/yucsum.h YU_RX_*)
 RX_IP_OK, RX_L4, RX_L4_OK, RX_INVALID = 1, 2, 4, 8
+RX_SPLIT = 16  # split_datagrams only (YU_RX_SPLIT): the packet's record, pay_len and payload are defined
 TX_MODES = (UDP, TCP, IPV4, ICMP, TX_DATAGRAM)
 MAX_TRANSPORT_LEN = 65535
 MAX_RAW_LEN = 0xFFFF0000  # include/yucsum.h YU_MAX_RAW_LEN
@@ -492,6 +493,104 @@ def build_datagrams(payload: torch.Tensor, pay_offsets: torch.Tensor, records: t
     check(rc, "yu_tx_build_ragged")
     out.build_tables = (po, do)  # the kernel reads them asynchronously: keep them alive with the result
     return dst, (do if dst_offsets is None else dst_offsets), out
+
+
+def split_datagrams(data: torch.Tensor, offsets: torch.Tensor, *, pay: torch.Tensor | None = None,
+                    pay_offsets: torch.Tensor | None = None, records: torch.Tensor | None = None,
+                    pay_len: torch.Tensor | None = None, out: torch.Tensor | None = None, validate: bool = False,
+                    stream: torch.cuda.Stream | None = None):
+    """Received IPv4 datagrams taken apart on the device (yu_rx_split_ragged), the inverse
+    of :func:`build_datagrams`: what ipv4.HandlePacket, Nic.DeliverTransportPacket,
+    segment.parse and udp.endpoint.HandlePacket do with a datagram once its checksums
+    are known. Packet i is ``data[offsets[i] : offsets[i+1]]`` (n+1 int64/uint64 offsets,
+    the batch :func:`checksum_ragged` takes). Returns ``(pay, pay_offsets, pay_len,
+    records, out)``: ``out[i]`` is ``verify_rx``'s flags plus :data:`RX_SPLIT`; where that
+    bit is set, ``records[i]`` (shape (n, 32) uint8, :func:`yustack_amd.packets.rx_records`
+    views it as ``TX_RECORD``) holds the header fields, ``pay_len[i]`` (int32) the payload's
+    length L and ``pay[pay_offsets[i] : pay_offsets[i] + L]`` the payload (for TCP it
+    starts with the option bytes); where it is not, the record is zero, ``pay_len[i]`` is 0
+    and nothing is stored in ``pay``.
+
+    ``pay_offsets=None``: the ``offsets`` tensor itself (a packet's own length is always
+    room enough), with no host read. ``pay=None``: a new tensor of ``max(data.numel(), 1)``
+    bytes. ``validate=True`` reads the tables and the headers back and raises
+    ValueError for offsets out of the call's contract (include/yucsum.h) or for a packet
+    whose payload, by its own header, has less room in ``pay`` than bytes (room of the
+    packet's length, as with ``pay_offsets=None``, always suffices). With every tensor
+    given the call is capturable in a graph."""
+    _dev_u8(data, "data")
+    dev = data.device
+    if not isinstance(offsets, torch.Tensor) or not offsets.is_cuda or offsets.device != dev:
+        raise TypeError(f"offsets must be a CUDA tensor on {dev}")
+    if offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError("offsets must hold n + 1 entries")
+    n = offsets.numel() - 1
+    o = _dev_index(offsets, "offsets", dev, n + 1)
+    po = o if pay_offsets is None else _dev_index(pay_offsets, "pay_offsets", dev, n + 1)
+    if o.data_ptr() % 8 or po.data_ptr() % 8:
+        raise TypeError("offsets and pay_offsets must be 8-byte aligned")
+    if pay is None:
+        pay = torch.empty(max(data.numel(), 1), dtype=torch.uint8, device=dev)
+    else:
+        _dev_u8(pay, "pay")
+        if pay.device != dev:
+            raise TypeError(f"pay must be on {dev}")
+        if _overlaps(pay, data):
+            raise ValueError("pay overlaps data")
+    if records is None:
+        records = torch.empty((max(n, 1), 32), dtype=torch.uint8, device=dev)[:n]
+    else:
+        _dev_u8(records, "records")
+        if records.device != dev:
+            raise TypeError(f"records must be on {dev}")
+        if records.dim() != 2 or records.shape != (n, 32):
+            raise ValueError("records must have shape (n, 32)")
+        if records.data_ptr() % 8:
+            raise TypeError("records must be 8-byte aligned")
+        if _overlaps(pay, records):
+            raise ValueError("pay overlaps records")
+    if pay_len is None:
+        pay_len = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    else:
+        pay_len = _opt(pay_len, torch.int32, n, dev, "pay_len")
+    if validate and n > 0:
+        plen = o[1:] - o[:-1]
+        room = po[1:] - po[:-1]
+        # what each header asks for: slen - H where IsValid holds and HL >= 20 (a packet
+        # the delivery tests then refuse stores nothing and needs no room)
+        byte = lambda k: data[(o[:-1] + k).clamp(0, data.numel() - 1)].to(torch.int64)  # noqa: E731
+        hl, tl, proto = (byte(0) & 15) * 4, byte(2) * 256 + byte(3), byte(9)
+        hdr = hl + 20 * (proto == 6) + 8 * (proto == 17) + 4 * (proto == 1)
+        need = torch.where((plen >= 20) & (hl >= 20) & (hl <= tl) & (tl <= plen), (tl - hdr).clamp(min=0), 0)
+        ok = torch.stack(((plen >= 0).all() & (o[0] >= 0) & (o[-1] <= data.numel()),
+                          (plen <= MAX_TRANSPORT_LEN).all(),
+                          (room >= 0).all() & (po[0] >= 0) & (po[-1] <= pay.numel()),
+                          (room >= need).all())).tolist()
+        if not ok[0]:
+            raise ValueError("offsets is not non-decreasing within data")
+        if not ok[1]:
+            raise ValueError("datagrams must be <= 65535 bytes")
+        if not ok[2]:
+            raise ValueError("pay_offsets is not non-decreasing within pay")
+        if not ok[3]:
+            raise ValueError("a packet's payload has less room in pay than bytes")
+    out = _result(out, n, dev)
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream(dev))
+        for t in (o, po, pay, records, pay_len, out):
+            t.record_stream(stream)
+    with torch.cuda.device(dev):
+        rc = lib().yu_rx_split_ragged(data.data_ptr(), o.data_ptr(), n, pay.data_ptr(), po.data_ptr(),
+                                      records.data_ptr() if n else None, pay_len.data_ptr() if n else None,
+                                      out.data_ptr() if n else None, _stream(dev, stream))
+    check(rc, "yu_rx_split_ragged")
+    out.split_tables = (o, po)  # the kernel reads them asynchronously: keep them alive with the result
+    return pay, (offsets if pay_offsets is None else pay_offsets), pay_len, records, out
+
+
+def split_variant(n: int = 1 << 20) -> str:
+    """Name of the kernel :func:`split_datagrams` launches for a batch of n packets."""
+    return _wave_variant("rx_split", n)
 
 
 def _wave_variant(call: str, n: int, mode=None, fill: bool = False) -> str:

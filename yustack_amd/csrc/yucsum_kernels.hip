@@ -87,6 +87,10 @@
 //     outgoing datagram, the payload as a single view through k_pack's store side,
 //     the header encoded and summed from a 32-byte record and stored last
 //     (yucsum_build.h).
+//   k_split<U, NT>: yu_rx_split_ragged (planned by yu::plan_split): one wave per
+//     received datagram, its first 80 bytes one dword per lane for the parse, the
+//     record and the header sums, the payload [HL + H, TL) as a single view
+//     through k_pack's store side (yucsum_split.h).
 //   All are grid-stride kernels; the grid is sized per CU and over-subscribed
 //   (see blocks_per_cu in yucsum_plan.cpp), except that k_seg narrows it for
 //   small packets (seg_waves).
@@ -105,6 +109,7 @@
 #include "yucsum_iov.h"
 #include "yucsum_iov_pack.h"
 #include "yucsum_plan.h"
+#include "yucsum_split.h"
 
 namespace {
 
@@ -3324,6 +3329,152 @@ __global__ __launch_bounds__(256) void k_build(const uint8_t *payload, const uin
 }
 
 // ---------------------------------------------------------------------
+// k_split<U, NT>: received IPv4 datagrams taken apart into a 32-byte record, a
+// payload and VERIFY_RX's flags (yu_rx_split_ragged; yucsum_split.h has the
+// arithmetic). k_build run backwards, on the same grid: one wave per packet.
+// A packet is one source range, so there is no view table and no gather: lane
+// j < 21 loads window dword j of the packet's first min(len, 80) bytes, a
+// packet ahead of the walk, and one ds_bpermute plus one v_alignbyte turn that
+// into packet dword k in lane k. The parse, the record and the reference's
+// delivery tests read those lanes with v_readlane; the IPv4 header, the pseudo
+// header's addresses and the H fixed transport bytes are summed from them.
+// The payload [HL + H, TL) is the only thing walked: U 1-KiB slots a step,
+// each summed (k_iov's slot sum) and stored through yucsum_iov_pack.h's plan,
+// shift and masked stores with nothing held back. A packet that does not split
+// is walked for its sum alone (no room: no store). The control data of a
+// packet, its offsets pair and its pay_offsets pair, are wave-uniform scalar
+// loads through the constant address space (no store of the call may touch the
+// tables, which may be one array) issued two packets ahead, so that the header
+// load of the next packet can be issued before the current one is walked. The
+// record is stored by lanes 0..7, pay_len and out by the lead lane.
+// ---------------------------------------------------------------------
+struct SplitArgs {
+  uint8_t *pay;
+  const uint64_t *pay_offsets;
+  uint32_t *recs;  // yu_tx_record as eight dwords
+  uint32_t *pay_len;
+  uint16_t *out;
+  uint64_t n;
+};
+
+struct SplitPkt {
+  uint64_t o0, o1;  // offsets[q], offsets[q + 1]
+  uint64_t p0, p1;  // pay_offsets[q], pay_offsets[q + 1]
+};
+
+template <int U, int NT>
+__global__ __launch_bounds__(256) void k_split(const uint8_t *data, const uint64_t *offsets_, SplitArgs A_) {
+  SplitArgs A = A_;  // what only addresses a vector store needs no scalar registers
+  A.pay = in_vgpr(A_.pay);
+  A.recs = in_vgpr(A_.recs);
+  A.pay_len = in_vgpr(A_.pay_len);
+  A.out = in_vgpr(A_.out);
+  const YU_CONST_AS uint64_t *offsets = const_as(offsets_);
+  const YU_CONST_AS uint64_t *pay_offsets = const_as(A.pay_offsets);
+  const uint32_t lane = threadIdx.x & 63u;
+  const bool lead = lane == 63;
+  const uint64_t wave = grid_wave(0u);
+  const uint64_t nwave = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  if (wave >= A.n) return;
+  const uint64_t oN = offsets[A.n], pN = pay_offsets[A.n];
+
+  // Packet q's control data (past the batch: an empty packet, nothing is loaded).
+  auto packet = [&](SplitPkt &P, uint64_t q) __attribute__((always_inline)) {
+    const uint64_t i = q < A.n ? q : 0;
+    P.o0 = offsets[i];
+    P.o1 = q < A.n ? offsets[i + 1] : P.o0;
+    P.p0 = pay_offsets[i];
+    P.p1 = pay_offsets[i + 1];
+  };
+  // Its header load: lane j's window dword j.
+  auto header = [&](const SplitPkt &P) __attribute__((always_inline)) -> uint32_t {
+    uint64_t addr;
+    uint32_t len;
+    yu::split_src((uint64_t)(uintptr_t)data, P.o0, P.o1, oN, addr, len);
+    const uint32_t lim = yu::split_hdr_lim(addr, len);
+    const uint64_t base = uniform64(addr & ~3ull);
+    const __amdgpu_buffer_rsrc_t r = rsrc_at(base, base + lim);
+    return __builtin_amdgcn_raw_buffer_load_b32(r, (int)(4u * lane < lim ? 4u * lane : kOOB), 0, 0);
+  };
+
+  const PackStore st;
+  SplitPkt cur, nx, nn;
+  packet(cur, wave);
+  packet(nx, wave + nwave);
+  uint32_t hw = header(cur);
+  for (uint64_t p = wave; p < A.n; p += nwave) {
+    const uint32_t hwn = header(nx);
+    packet(nn, p + 2 * nwave);
+    uint64_t addr;
+    uint32_t len;
+    yu::split_src((uint64_t)(uintptr_t)data, cur.o0, cur.o1, oN, addr, len);
+    // packet dword k in lane k (lanes past the header: zeros)
+    const uint32_t up = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(4u * ((lane + 1u) & 63u)), (int)hw);
+    const int pd = (int)yu::split_pkt_dword(up, hw, (uint32_t)addr & 3u);
+    const uint32_t d0 = (uint32_t)__builtin_amdgcn_readlane(pd, 0), d1 = (uint32_t)__builtin_amdgcn_readlane(pd, 1);
+    const uint32_t d2 = (uint32_t)__builtin_amdgcn_readlane(pd, 2), d3 = (uint32_t)__builtin_amdgcn_readlane(pd, 3);
+    const uint32_t d4 = (uint32_t)__builtin_amdgcn_readlane(pd, 4);
+    const int q = (int)(d0 & 15u);  // IHL: the transport header's first dword
+    const uint32_t t0 = (uint32_t)__builtin_amdgcn_readlane(pd, q), t1 = (uint32_t)__builtin_amdgcn_readlane(pd, q + 1);
+    const uint32_t t2 = (uint32_t)__builtin_amdgcn_readlane(pd, q + 2);
+    const uint32_t t3 = (uint32_t)__builtin_amdgcn_readlane(pd, q + 3);
+    yu::SplitDg S;
+    yu::split_parse(S, len, d0, d2, t1, t3);
+    const uint32_t hs = group_total<64>(yu::split_ip_term(S, lane, (uint32_t)pd));
+    const uint32_t xs = group_total<64>(yu::split_seg_term(S, lane, (uint32_t)pd));
+
+    const yu::IovPackDst D = yu::split_dst(S, (uint64_t)(uintptr_t)A.pay, cur.p0, cur.p1, pN);
+    yu::IovWalk W;
+    const int32_t vpk = yu::split_walk(W, S, addr);
+    uint32_t accA = 0, accB = 0;
+    uint32_t cprev = 0;  // lane 63: the last source dword of the slot before
+    while (!yu::iov_walk_done(W)) {
+      uint32_t info[U];
+      int32_t po[U];
+      uint4 c[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        po[u] = yu::iov_pack_po(vpk, W.w, lane);
+        yu::IovSlot Sl;
+        yu::iov_walk_slot(W, Sl);
+        info[u] = Sl.info;
+        c[u] = iov_slot_load<NT>(Sl, lane, u);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (yu::iov_lim(info[u]) == 0) continue;  // an empty slot (wave-uniform)
+        const uint32_t t = iov_slot_sum(c[u], info[u], lane);
+        const bool swap = (info[u] & yu::kIovSwap) != 0;
+        yu::IovPackPlan P;
+        yu::iov_pack_plan(P, info[u], D, po[u], lane);
+        const uint32_t prev = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(4u * ((lane - 1u) & 63u)),
+                                                                     (int)(lead ? cprev : c[u].w));
+        yu::iov_pack_lane(st, P, lane, c[u].x, c[u].y, c[u].z, c[u].w, prev, -1, -1);
+        cprev = c[u].w;
+        accA += swap ? t : 0u;
+        accB += swap ? 0u : t;
+      }
+    }
+    const uint32_t sA = group_total<64>(accA), sB = group_total<64>(accB);
+    if (lead) {
+      A.out[p] = (uint16_t)yu::split_value(S, len, hs, xs, sA, sB);
+      A.pay_len[p] = S.L;
+    }
+    {
+      yu::BuildRec R;
+      yu::split_record(R, S, d0, d1, d2, d3, d4, t0, t1, t2, t3);
+      uint32_t w = R.w[0];
+#pragma unroll
+      for (int k = 1; k < 8; ++k) w = lane == (uint32_t)k ? R.w[k] : w;
+      if (lane < 8u) A.recs[8 * p + lane] = w;
+    }
+    cur = nx;
+    nx = nn;
+    hw = hwn;
+  }
+}
+
+// ---------------------------------------------------------------------
 // Host side: launch. Which kernel, form, load policy and grid a batch gets is
 // yu::plan's decision (yucsum_plan.cpp); here are the functions it names.
 // ---------------------------------------------------------------------
@@ -3619,6 +3770,29 @@ int tx_build(const uint8_t *payload, const uint64_t *pay_offsets, const yu_tx_re
   return launch_wave(&WaveFns::build, yu::WaveFamily::Build, n, 0, false, stream, payload, pay_offsets, recs, a);
 }
 
+// yu_rx_split_ragged: k_split by load policy. It is not a row of kWaveFns: no
+// family of YU_WAVE_KERNELS asks for it, and yu::plan_split plans it with the
+// same grid arithmetic (yucsum_plan.h).
+void (*const kSplitFns[3])(const uint8_t *, const uint64_t *, SplitArgs) = {k_split<4, 0>, k_split<4, 1>,
+                                                                            k_split<4, 2>};
+
+int rx_split(const uint8_t *data, const uint64_t *offsets, uint64_t n, uint8_t *pay, const uint64_t *pay_offsets,
+             yu_tx_record *recs, uint32_t *pay_len, uint16_t *out, void *stream) {
+  if (!aligned(out, 2) || !aligned(pay_len, 4)) return YU_EINVAL;  // EINVAL:side-align
+  if (n == 0) return YU_OK;
+  if (!out) return YU_EINVAL;  // EINVAL:out
+  if (!offsets || !aligned(offsets, 8) || !pay_offsets || !aligned(pay_offsets, 8) || !aligned(recs, 8))
+    return YU_EINVAL;  // EINVAL:offsets
+  if (!data || !pay || !recs || !pay_len) return YU_EINVAL;  // EINVAL:data
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return hip_status(e);
+  const yu::SplitPlan p = yu::plan_split(n, cu_count(dev), yu::env_knobs());
+  const SplitArgs a = {pay, pay_offsets, (uint32_t *)recs, pay_len, out, n};
+  hipLaunchKernelGGL(kSplitFns[p.policy], dim3(p.blocks), dim3(256), 0, (hipStream_t)stream, data, offsets, a);
+  return hip_status(hipGetLastError());
+}
+
 // Completion signal for the host path's direct mode (yucsum_internal.h):
 // stored after the work before it on the stream, with system-scope release,
 // into coherent pinned host memory.
@@ -3748,6 +3922,16 @@ int yu_tx_build_ragged(const uint8_t *payload, const uint64_t *pay_offsets, cons
 
 const char *yu_tx_build_variant_n(uint64_t n) {
   return yu::plan_wave(yu::WaveFamily::Build, n, 0, false, 256, yu::env_knobs()).name;
+}
+
+int yu_rx_split_ragged(const uint8_t *data, const uint64_t *offsets, uint64_t n, uint8_t *pay,
+                       const uint64_t *pay_offsets, yu_tx_record *recs, uint32_t *pay_len, uint16_t *out,
+                       void *stream) {
+  return rx_split(data, offsets, n, pay, pay_offsets, recs, pay_len, out, stream);
+}
+
+const char *yu_rx_split_variant_n(uint64_t n) {
+  return yu::plan_split(n, 256, yu::env_knobs()).name;
 }
 
 const char *yu_uniform_variant(uint64_t stride, uint32_t len, int mode,

@@ -283,6 +283,18 @@ Plan plan(const Shape &s, int cus, const Knobs &k) {
   return p;
 }
 
+namespace {
+// The policy and the grid of a wave-per-packet launch (plan_wave, plan_split).
+void wave_grid(uint64_t n, int cus, const Knobs &k, uint8_t &policy, uint32_t &blocks_out) {
+  policy = (uint8_t)(k.nt >= 0 ? k.nt : 2);
+  const uint64_t cap = (uint64_t)cus * (k.blocks_per_cu ? k.blocks_per_cu : 64u);
+  uint64_t blocks = (n + 3) / 4;  // 4 waves per block, a wave per packet
+  if (blocks > cap) blocks = cap;
+  if (blocks < 1) blocks = 1;
+  blocks_out = (uint32_t)blocks;
+}
+}  // namespace
+
 // The wave-per-packet kernels: a wave per packet, four per block, on the over-
 // subscribed grid of the other wave-per-packet kernels (64 blocks per CU,
 // YU_BLOCKS_PER_CU overrides); the load policy is YU_NT's, else slot 2 (k_pack's
@@ -309,12 +321,15 @@ WavePlan plan_wave(WaveFamily family, uint64_t n, int mode, bool fill, int cus, 
   WavePlan p;
   p.kernel = (WaveKernel)id;
   p.name = rows[id].name;
-  p.policy = (uint8_t)(k.nt >= 0 ? k.nt : 2);
-  const uint64_t cap = (uint64_t)cus * (k.blocks_per_cu ? k.blocks_per_cu : 64u);
-  uint64_t blocks = (n + 3) / 4;  // 4 waves per block, a wave per packet
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  p.blocks = (uint32_t)blocks;
+  wave_grid(n, cus, k, p.policy, p.blocks);
+  return p;
+}
+
+// k_split: the same grid and policy (it reads each packet once, as k_build does).
+SplitPlan plan_split(uint64_t n, int cus, const Knobs &k) {
+  SplitPlan p;
+  p.name = "k_split<4>";
+  wave_grid(n, cus, k, p.policy, p.blocks);
   return p;
 }
 

@@ -213,6 +213,18 @@ struct WavePlan {
 // the dg kernels, every other the whole-packet ones. Build: mode and fill are ignored.
 WavePlan plan_wave(WaveFamily family, uint64_t n, int mode, bool fill, int cus, const Knobs &k);
 
+// yu_rx_split_ragged (k_split, yucsum_split.h) has one kernel and a plan beside
+// plan_wave, not a tenth row of YU_WAVE_KERNELS: the table's rows are what a
+// (family, dg, fill) of the scatter-gather, packing and building calls resolves
+// to, and no such call ever resolves to k_split. The policy and the grid are
+// plan_wave's own arithmetic, one copy of it.
+struct SplitPlan {
+  uint8_t policy;  // as WavePlan's
+  uint32_t blocks;
+  const char *name;  // what yu_rx_split_variant_n returns
+};
+SplitPlan plan_split(uint64_t n, int cus, const Knobs &k);
+
 }  // namespace yu
 #pragma GCC visibility pop
 

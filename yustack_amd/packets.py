@@ -16,6 +16,10 @@ and the test harnesses' inbound builders:
 and the record layout of the device-side sender, ``batch.build_datagrams``:
 
 * :data:`TX_RECORD`, :func:`tx_records`  struct yu_tx_record (include/yucsum.h)
+
+which is also what the device-side receiver, ``batch.split_datagrams``, fills in:
+
+* :data:`RX_SPLIT`, :func:`rx_records`   YU_RX_SPLIT and the records as ``TX_RECORD``
 """
 from __future__ import annotations
 
@@ -152,3 +156,19 @@ def tx_records(n: int, *, src=0, dst=0, sport=0, dport=0, seq=0, ack=0, window=0
                     ("tos", tos), ("frag", frag)):
         recs[name] = np.broadcast_to(np.asarray(a), (n,))
     return recs
+
+
+# YU_RX_SPLIT (include/yucsum.h): the bit batch.split_datagrams adds to VERIFY_RX's flags
+# when a packet's record, pay_len and payload are defined.
+RX_SPLIT = 16
+
+
+def rx_records(records) -> np.ndarray:
+    """The ``records`` tensor of ``batch.split_datagrams`` (shape (n, 32) uint8, on any
+    device) as a host array of n :data:`TX_RECORD` entries; a packet without
+    :data:`RX_SPLIT` has an all-zero record."""
+    raw = records.cpu().numpy() if hasattr(records, "cpu") else np.asarray(records)
+    raw = np.ascontiguousarray(raw, dtype=np.uint8)
+    if raw.ndim != 2 or raw.shape[1] != TX_RECORD.itemsize:
+        raise ValueError("records must have shape (n, 32)")
+    return raw.view(TX_RECORD).reshape(raw.shape[0])
