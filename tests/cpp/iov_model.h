@@ -1,10 +1,11 @@
 // What the CPU models of the wave-per-packet kernels share (iov_combine.cpp,
-// iov_datagram.cpp, iov_pack.cpp, iov_pack_datagram.cpp, tx_build.cpp): source
-// views in exact-size heap blocks, the dword a buffer load returns, the
-// destination block that counts its stores, the scalar compositions the kernels
-// are held against, the datagram generator, and the counters with the last line
-// every program prints. Each program keeps its own transcription of its kernel's
-// step and its own case loops.
+// iov_datagram.cpp, iov_pack.cpp, iov_pack_datagram.cpp, tx_build.cpp,
+// rx_split.cpp): source views in exact-size heap blocks, the dword a buffer load
+// returns, the destination block that counts its stores, the model of
+// range_walk (the single-range walk of k_build and k_split), the scalar
+// compositions the kernels are held against, the datagram generator, and the
+// counters with the last line every program prints. Each program keeps its own
+// transcription of the rest of its kernel's step and its own case loops.
 #ifndef YU_TESTS_IOV_MODEL_H
 #define YU_TESTS_IOV_MODEL_H
 
@@ -18,6 +19,7 @@
 
 #include "yucsum.h"
 #include "yucsum_iov.h"
+#include "yucsum_iov_pack.h"
 
 inline int fails = 0;
 inline uint64_t checks = 0;
@@ -96,6 +98,45 @@ struct Store {
     b32(a + 12, w);
   }
 };
+
+// range_walk<4, *> of yucsum_kernels.hip as k_build and k_split drive it: W is on
+// the packet's one range and vpk taken from it; steps of U = 4 slots, 64 lanes of
+// 4 dwords, each lane's previous source dword taken from its neighbour, lane 0's
+// from lane 63 of the slot before, every byte stored through st with nothing
+// held back. A, B: the two class sums (swapped, plain).
+inline void range_walk(yu::IovWalk &W, int32_t vpk, const yu::IovPackDst &D, Store &st, uint32_t &A, uint32_t &B) {
+  constexpr int kU = 4;
+  uint32_t cprev = 0;
+  A = B = 0;
+  while (!yu::iov_walk_done(W)) {
+    yu::IovSlot S[kU];
+    int32_t pk0[kU];
+    for (int u = 0; u < kU; ++u) {
+      pk0[u] = yu::iov_pack_po(vpk, W.w, 0);
+      yu::iov_walk_slot(W, S[u]);
+    }
+    for (int u = 0; u < kU; ++u) {
+      const uint32_t info = S[u].info, lim = yu::iov_lim(info), hm = yu::iov_head_mask(info);
+      if (lim == 0) continue;
+      uint32_t c[64][4];
+      uint32_t t = 0;
+      for (uint32_t lane = 0; lane < 64; ++lane)
+        for (uint32_t j = 0; j < 4; ++j) {
+          const uint32_t cr = 16u * lane + 4u * j;
+          c[lane][j] = 16u * lane < lim ? load_dword(S[u], cr, lim) : 0u;  // the other lanes load nothing
+          t = yu::iov_add(yu::iov_dword(c[lane][j], cr, lim, hm), t);
+        }
+      for (uint32_t lane = 0; lane < 64; ++lane) {
+        yu::IovPackPlan P;
+        yu::iov_pack_plan(P, info, D, pk0[u] + (int32_t)(16u * lane), lane);
+        const uint32_t prev = lane ? c[lane - 1][3] : cprev;
+        yu::iov_pack_lane(st, P, lane, c[lane][0], c[lane][1], c[lane][2], c[lane][3], prev, -1, -1);
+      }
+      cprev = c[63][3];
+      ((info & yu::kIovSwap) ? A : B) += t;
+    }
+  }
+}
 
 // The whole-packet modes: the scalar composition over the concatenated bytes
 // (include/yucsum.h modes).

@@ -2,9 +2,10 @@
 // and the value of yustack_amd/csrc/yucsum_split.h, the single-view walk of
 // yucsum_iov.h and the destination geometry of yucsum_iov_pack.h, driven here
 // exactly as the kernel drives them (the header as one window dword per lane,
-// packet dword k from lanes k and k + 1; steps of U = 4 slots, 64 lanes of 16
-// bytes, each lane's previous source dword taken from its neighbour, lane 0's
-// from lane 63 of the slot before), against a byte-by-byte restatement of what
+// packet dword k from lanes k and k + 1; the payload by iov_model.h's
+// range_walk: steps of U = 4 slots, 64 lanes of 16 bytes, each lane's previous
+// source dword taken from its neighbour, lane 0's from lane 63 of the slot
+// before), against a byte-by-byte restatement of what
 // ipv4.HandlePacket, Nic.DeliverTransportPacket, segment.parse and
 // udp.endpoint.HandlePacket do with a datagram, its checksums by the scalar
 // library's yu_checksum.
@@ -33,7 +34,6 @@
 
 namespace {
 
-constexpr int kU = 4;
 constexpr size_t kCanary = 48;
 
 struct Result {
@@ -65,35 +65,8 @@ Result kernel_split(Store &st, uint64_t data, uint64_t o0, uint64_t o1, uint64_t
   const yu::IovPackDst D = yu::split_dst(S, pay, p0, p1, pN);
   yu::IovWalk W;
   const int32_t vpk = yu::split_walk(W, S, addr);
-  uint32_t A = 0, B = 0, cprev = 0;
-  while (!yu::iov_walk_done(W)) {
-    yu::IovSlot Sl[kU];
-    int32_t pk0[kU];
-    for (int u = 0; u < kU; ++u) {
-      pk0[u] = yu::iov_pack_po(vpk, W.w, 0);
-      yu::iov_walk_slot(W, Sl[u]);
-    }
-    for (int u = 0; u < kU; ++u) {
-      const uint32_t info = Sl[u].info, slim = yu::iov_lim(info), hm = yu::iov_head_mask(info);
-      if (slim == 0) continue;
-      uint32_t c[64][4];
-      uint32_t t = 0;
-      for (uint32_t lane = 0; lane < 64; ++lane)
-        for (uint32_t j = 0; j < 4; ++j) {
-          const uint32_t cr = 16u * lane + 4u * j;
-          c[lane][j] = 16u * lane < slim ? load_dword(Sl[u], cr, slim) : 0u;  // the other lanes load nothing
-          t = yu::iov_add(yu::iov_dword(c[lane][j], cr, slim, hm), t);
-        }
-      for (uint32_t lane = 0; lane < 64; ++lane) {
-        yu::IovPackPlan P;
-        yu::iov_pack_plan(P, info, D, pk0[u] + (int32_t)(16u * lane), lane);
-        const uint32_t prev = lane ? c[lane - 1][3] : cprev;
-        yu::iov_pack_lane(st, P, lane, c[lane][0], c[lane][1], c[lane][2], c[lane][3], prev, -1, -1);
-      }
-      cprev = c[63][3];
-      ((info & yu::kIovSwap) ? A : B) += t;
-    }
-  }
+  uint32_t A, B;
+  range_walk(W, vpk, D, st, A, B);
   Result r;
   r.out = yu::split_value(S, len, hs, xs, A, B);
   r.pay_len = S.L;

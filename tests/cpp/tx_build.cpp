@@ -1,11 +1,11 @@
 // k_build on a CPU: the header encode, sums and contract test of
 // yustack_amd/csrc/yucsum_build.h, the single-view walk of yucsum_iov.h and the
 // destination geometry of yucsum_iov_pack.h, driven here exactly as the kernel
-// drives them (steps of U = 4 slots, 64 lanes of 16 bytes, each lane's previous
-// source dword taken from its neighbour, lane 0's from lane 63 of the slot
-// before; the header stored last, lane J < 11 its destination dword J, the
-// neighbour's source dword by a row shift), against an image assembled byte by
-// byte with the scalar library's yu_checksum.
+// drives them (the payload by iov_model.h's range_walk: steps of U = 4 slots, 64
+// lanes of 16 bytes, each lane's previous source dword taken from its neighbour,
+// lane 0's from lane 63 of the slot before; the header stored last, lane J < 11
+// its destination dword J, the neighbour's source dword by a row shift), against
+// an image assembled byte by byte with the scalar library's yu_checksum.
 //
 // Each datagram is built into an exact-size heap block with 0xA5 canaries on
 // both sides; a store is counted per byte, so a byte stored twice, a slack byte
@@ -26,7 +26,6 @@
 
 namespace {
 
-constexpr int kU = 4;
 constexpr size_t kCanary = 48;
 
 struct Result {
@@ -51,35 +50,8 @@ Result kernel_build(Store &st, uint64_t payload, uint64_t p0, uint64_t p1, uint6
   const int32_t vpk = yu::iov_pack_view(addr, W.off);
   yu::iov_walk_view(W, addr, plen, false, 0u);
   const uint32_t L = W.off - (yu::kBuildIp + H);
-  uint32_t A = 0, B = 0, cprev = 0;
-  while (!yu::iov_walk_done(W)) {
-    yu::IovSlot S[kU];
-    int32_t pk0[kU];
-    for (int u = 0; u < kU; ++u) {
-      pk0[u] = yu::iov_pack_po(vpk, W.w, 0);
-      yu::iov_walk_slot(W, S[u]);
-    }
-    for (int u = 0; u < kU; ++u) {
-      const uint32_t info = S[u].info, lim = yu::iov_lim(info), hm = yu::iov_head_mask(info);
-      if (lim == 0) continue;
-      uint32_t c[64][4];
-      uint32_t t = 0;
-      for (uint32_t lane = 0; lane < 64; ++lane)
-        for (uint32_t j = 0; j < 4; ++j) {
-          const uint32_t cr = 16u * lane + 4u * j;
-          c[lane][j] = 16u * lane < lim ? load_dword(S[u], cr, lim) : 0u;  // the other lanes load nothing
-          t = yu::iov_add(yu::iov_dword(c[lane][j], cr, lim, hm), t);
-        }
-      for (uint32_t lane = 0; lane < 64; ++lane) {
-        yu::IovPackPlan P;
-        yu::iov_pack_plan(P, info, D, pk0[u] + (int32_t)(16u * lane), lane);
-        const uint32_t prev = lane ? c[lane - 1][3] : cprev;
-        yu::iov_pack_lane(st, P, lane, c[lane][0], c[lane][1], c[lane][2], c[lane][3], prev, -1, -1);
-      }
-      cprev = c[63][3];
-      ((info & yu::kIovSwap) ? A : B) += t;
-    }
-  }
+  uint32_t A, B;
+  range_walk(W, vpk, D, st, A, B);
   Result r;
   yu::build_values(R, H, L, A, B, r.ipsum, r.xsum);
   uint32_t hw[64];

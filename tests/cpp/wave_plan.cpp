@@ -1,6 +1,6 @@
 // Prints yu::plan_wave (yustack_amd/csrc/yucsum_plan.h) for the batches named on
-// the command line: `wave_plan family n mode fill cus [...]` (family: iov, pack or
-// build), one line "kernel policy blocks name" each; the argument `enum` prints
+// the command line: `wave_plan family n mode fill cus [...]` (family: iov, pack,
+// build or split), one line "kernel policy blocks name" each; the argument `enum` prints
 // one line with the values of the yu::WaveKernel enumerators in order and their
 // count. The knobs come from the environment as in the library (YU_TUNING=1 and
 // YU_NT / YU_BLOCKS_PER_CU). CPU only.
@@ -26,6 +26,7 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[i], "iov")) family = yu::WaveFamily::Iov;
     else if (!strcmp(argv[i], "pack")) family = yu::WaveFamily::Pack;
     else if (!strcmp(argv[i], "build")) family = yu::WaveFamily::Build;
+    else if (!strcmp(argv[i], "split")) family = yu::WaveFamily::Split;
     else return 2;
     const yu::WavePlan p = yu::plan_wave(family, strtoull(argv[i + 1], nullptr, 10), atoi(argv[i + 2]),
                                          atoi(argv[i + 3]) != 0, atoi(argv[i + 4]), yu::env_knobs());

@@ -10,7 +10,8 @@ CPP = os.path.join(ROOT, "tests", "cpp")
 INC = [f"-I{ROOT}/include", f"-I{ROOT}/yustack_amd/csrc"]
 SCALAR = os.path.join(ROOT, "yustack_amd", "csrc", "yucsum_scalar.cpp")
 SAN_FLAGS = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
-MODELS = ("iov_combine.cpp", "iov_datagram.cpp", "iov_pack.cpp", "iov_pack_datagram.cpp", "tx_build.cpp")
+MODELS = ("iov_combine.cpp", "iov_datagram.cpp", "iov_pack.cpp", "iov_pack_datagram.cpp", "tx_build.cpp",
+          "rx_split.cpp")
 
 
 def build_and_run(tmp_path, program, sources=(SCALAR,), sanitize=False, ends="packets ok"):
@@ -30,7 +31,7 @@ def build_and_run(tmp_path, program, sources=(SCALAR,), sanitize=False, ends="pa
 
 
 def models_compile():
-    """The five CPU models of the wave-per-packet kernels compile against the library's
+    """The six CPU models of the wave-per-packet kernels compile against the library's
     headers as they are."""
     for src in MODELS:
         r =subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-O1", "-fsyntax-only", *INC,

@@ -151,7 +151,7 @@ def pack_plan():
 def test_enum_values_keep_their_meaning(pack_plan):
     _, enum = pack_plan([])
     assert enum[:8] == [0, 1, 2, 3, 4, 5, 6, 7]
-    assert enum[8:] == [8, 9]  # k_build4, then the count
+    assert enum[8:] == [8, 9, 10]  # k_build4, k_split4, then the count
 
 
 def test_plan_rows_for_the_datagram_modes(pack_plan):

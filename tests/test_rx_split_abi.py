@@ -1,7 +1,7 @@
 """The device-side receiver at the C-ABI boundary (include/yucsum.h, yu_rx_split_ragged /
 yu_rx_split_variant_n / YU_RX_SPLIT): exported and declared, every documented YU_EINVAL
 returned before any device work with the output arrays untouched, the empty batch,
-YU_ENODEV without a device, the kernel yu::plan_split names, its grid and its knobs
+YU_ENODEV without a device, the kernel yu::plan_wave names, its grid and its knobs
 behind the gate, what the Python front end refuses and what packets.rx_records views.
 CPU only: no call here reaches a device (the arguments are refused first, or there is no
 device)."""
@@ -14,10 +14,10 @@ import numpy as np
 import pytest
 import torch
 
+import wave_plan
 from yustack_amd import _lib, batch, packets
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "yustack_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "yucsum.h")
 NAMES = ("yu_rx_split_ragged", "yu_rx_split_variant_n")
 
@@ -105,39 +105,25 @@ def test_variant_name():
     assert batch.split_variant() == "k_split<4>"
 
 
-@pytest.fixture(scope="module")
-def split_plan(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("split_plan") / "split_plan")
-    r = subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", f"-I{ROOT}/include", "-D__HIP_PLATFORM_AMD__",
-                        "-I/opt/rocm/include", f"-I{CSRC}", os.path.join(ROOT, "tests", "cpp", "split_plan.cpp"),
-                        os.path.join(CSRC, "yucsum_plan.cpp"), "-o", exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-
-    def plans(cases, env=None):
-        e = {k: v for k, v in os.environ.items() if not k.startswith("YU_")}
-        e.update(env or {})
-        r = subprocess.run([exe, *[str(x) for c in cases for x in c]], capture_output=True, text=True, timeout=60,
-                           env=e)
-        assert r.returncode == 0, r.stderr[-2000:]
-        rows = [line.split(maxsplit=2) for line in r.stdout.splitlines()]
-        assert len(rows) == len(cases)
-        return [(int(pol), int(blocks), name) for pol, blocks, name in rows]
-    return plans
+def split_plans(cases, env=None):
+    """[(kernel, policy, blocks, name)] for the (n, cus) cases."""
+    return wave_plan.plans("split", [(n, 0, 0, cus) for n, cus in cases], env)
 
 
-def test_plan_rows(split_plan):
-    rows = split_plan([(n, cus) for n in (1, 4, 5, 4097, 1 << 20) for cus in (64, 256, 304)])
-    assert all(r[0] == 2 and r[2] == "k_split<4>" for r in rows)
-    assert [r[1] for r in rows[-3:]] == [64 * 64, 256 * 64, 304 * 64]   # 64 blocks per CU
-    assert [r[1] for r in rows[0:12:3]] == [1, 1, 2, 1025]              # a wave per packet, four per block
+def test_plan_rows():
+    rows = split_plans([(n, cus) for n in (1, 4, 5, 4097, 1 << 20) for cus in (64, 256, 304)])
+    assert all(r[0] == 9 and r[1] == 2 and r[3] == "k_split<4>" for r in rows)
+    assert [r[2] for r in rows[-3:]] == [64 * 64, 256 * 64, 304 * 64]   # 64 blocks per CU
+    assert [r[2] for r in rows[0:12:3]] == [1, 1, 2, 1025]              # a wave per packet, four per block
 
 
-def test_plan_honours_the_knobs_behind_the_gate(split_plan):
+def test_plan_honours_the_knobs_behind_the_gate():
     case = [(1 << 20, 256)]
-    plain = split_plan(case)[0]
-    assert plain == (2, 256 * 64, "k_split<4>")
-    assert split_plan(case, {"YU_NT": "0", "YU_BLOCKS_PER_CU": "1"})[0] == plain  # gate closed
-    assert split_plan(case, {"YU_TUNING": "1", "YU_NT": "0", "YU_BLOCKS_PER_CU": "1"})[0] == (0, 256, "k_split<4>")
+    plain = split_plans(case)[0]
+    assert plain[1:] == (2, 256 * 64, "k_split<4>")
+    assert split_plans(case, {"YU_NT": "0", "YU_BLOCKS_PER_CU": "1"})[0] == plain  # gate closed
+    tuned = split_plans(case, {"YU_TUNING": "1", "YU_NT": "0", "YU_BLOCKS_PER_CU": "1"})[0]
+    assert tuned[1:] == (0, 256, "k_split<4>")
 
 
 def test_python_front_end_refuses_before_the_library():

@@ -4,8 +4,10 @@ returned before the one table replaced them (recorded from their printers; k_bui
 row 0 of its own enum, written as row 8), one line `family n mode fill cus | env | kernel
 policy blocks name` per case: iov and pack for mode 0..9 x fill 0, 1 x n 1, 5, 4097, 2^20
 x 64, 256, 304 CUs, build for the same n x CUs, each with no knobs, with knobs behind the
-closed gate and under three YU_TUNING=1 sets. tests/cpp/wave_plan.cpp reproduces every
-line. CPU only."""
+closed gate and under three YU_TUNING=1 sets. The split lines at its end are what
+yu::plan_split returned for the same n x CUs x knobs before k_split became row 9 of the
+table (recorded from its printer, which had no kernel id: written as row 9).
+tests/cpp/wave_plan.cpp reproduces every line. CPU only."""
 import os
 
 import wave_plan
@@ -20,7 +22,7 @@ def test_wave_plans_match_the_record():
     for k, line in enumerate(want):
         case, env, _ = line.split(" | ")
         by_env.setdefault(env, []).append((k, case.split()))
-    assert len(want) == 5 * (2 * 10 * 2 * 4 * 3 + 4 * 3) and len(by_env) == 5
+    assert len(want) == 5 * (2 * 10 * 2 * 4 * 3 + 4 * 3 + 4 * 3) and len(by_env) == 5
     for env, cases in by_env.items():
         e = dict(kv.split("=") for kv in env.split()) if env != "-" else None
         got = wave_plan.run([x for _, c in cases for x in c], e)
@@ -28,5 +30,5 @@ def test_wave_plans_match_the_record():
         for (k, c), g in zip(cases, got):
             assert f"{' '.join(c)} | {env} | {g}" == want[k], f"wave_plans.txt:{k + 1}: the plan changed"
     # every row of the table is planned somewhere in the record
-    assert {line.split(" | ")[2].split()[0] for line in want} == {str(k) for k in range(9)}
-    assert wave_plan.enum() == list(range(10))
+    assert {line.split(" | ")[2].split()[0] for line in want} == {str(k) for k in range(10)}
+    assert wave_plan.enum() == list(range(11))

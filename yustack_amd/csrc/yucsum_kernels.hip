@@ -87,10 +87,11 @@
 //     outgoing datagram, the payload as a single view through k_pack's store side,
 //     the header encoded and summed from a 32-byte record and stored last
 //     (yucsum_build.h).
-//   k_split<U, NT>: yu_rx_split_ragged (planned by yu::plan_split): one wave per
+//   k_split<U, NT>: yu_rx_split_ragged (planned by yu::plan_wave): one wave per
 //     received datagram, its first 80 bytes one dword per lane for the parse, the
 //     record and the header sums, the payload [HL + H, TL) as a single view
-//     through k_pack's store side (yucsum_split.h).
+//     through k_pack's store side (yucsum_split.h). k_build and k_split walk
+//     their one range with the same function, range_walk.
 //   All are grid-stride kernels; the grid is sized per CU and over-subscribed
 //   (see blocks_per_cu in yucsum_plan.cpp), except that k_seg narrows it for
 //   small packets (seg_waves).
@@ -3202,17 +3203,67 @@ __global__ __launch_bounds__(256) void k_pack_dg(const yu_iovec *views_, const u
 }
 
 // ---------------------------------------------------------------------
+// range_walk<U, NT>: the walk of a packet that is one source range, shared by
+// k_build and k_split. The caller has positioned W on the range (iov_walk_view)
+// and taken vpk from it; here the range goes by in steps of U 1-KiB slots, each
+// summed (k_iov's slot sum) and stored through yucsum_iov_pack.h's plan, shift
+// and masked stores with nothing held back, a lane's previous source dword from
+// its neighbour by ds_bpermute (lane 0's from lane 63 of the slot before).
+// Returns the lane's two class sums {swapped, plain}; the walk is handed back
+// as it ends (k_build reads its `over`). The shape is the one the compiler
+// follows most closely to the loop written out in each kernel: the walk on a
+// local copy declared ahead of the sums, everything else by const value. By
+// reference, or by value without the const, both kernels take one VGPR more;
+// walking the caller's W in place lays k_build's loop out differently
+// (profiles/r15/range_walk_isa_r15.txt).
+// ---------------------------------------------------------------------
+template <int U, int NT>
+__device__ __forceinline__ uint2 range_walk(yu::IovWalk &walk, const int32_t vpk, const yu::IovPackDst D,
+                                            const PackStore st, const uint32_t lane, const bool lead) {
+  yu::IovWalk W = walk;
+  uint32_t accA = 0, accB = 0;
+  uint32_t cprev = 0;  // lane 63: the last source dword of the slot before
+  while (!yu::iov_walk_done(W)) {
+    uint32_t info[U];
+    int32_t po[U];
+    uint4 c[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      po[u] = yu::iov_pack_po(vpk, W.w, lane);
+      yu::IovSlot S;
+      yu::iov_walk_slot(W, S);
+      info[u] = S.info;
+      c[u] = iov_slot_load<NT>(S, lane, u);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (yu::iov_lim(info[u]) == 0) continue;  // an empty slot (wave-uniform)
+      const uint32_t t = iov_slot_sum(c[u], info[u], lane);
+      const bool swap = (info[u] & yu::kIovSwap) != 0;
+      yu::IovPackPlan P;
+      yu::iov_pack_plan(P, info[u], D, po[u], lane);
+      const uint32_t prev = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(4u * ((lane - 1u) & 63u)),
+                                                                   (int)(lead ? cprev : c[u].w));
+      yu::iov_pack_lane(st, P, lane, c[u].x, c[u].y, c[u].z, c[u].w, prev, -1, -1);
+      cprev = c[u].w;
+      accA += swap ? t : 0u;
+      accB += swap ? 0u : t;
+    }
+  }
+  walk = W;
+  return make_uint2(accA, accB);
+}
+
+// ---------------------------------------------------------------------
 // k_build<U, NT>: outgoing IPv4 datagrams built from a payload and one 32-byte
 // record per packet (yu_tx_build_ragged; yucsum_build.h has the arithmetic). One
 // wave per packet on the over-subscribed grid, as k_loop and k_iov. It is
 // k_pack's store side fed by exactly one source range: the payload is a single
-// view, walked from packet offset 20 + H in steps of U 1-KiB slots, each summed
-// (k_iov's slot sum) and stored through yucsum_iov_pack.h's plan, shift and
-// masked stores with nothing held back. There is no view table, no gather and
-// no parse: the control data of a packet is its pay_offsets pair, its
-// dst_offsets pair and its record (two 16-byte loads), all wave-uniform scalar
-// loads through the constant address space (no store of the call may touch the
-// tables) issued a packet ahead. The header's sums are arithmetic on the
+// view, walked from packet offset 20 + H by range_walk. There is no view table,
+// no gather and no parse: the control data of a packet is its pay_offsets pair,
+// its dst_offsets pair and its record (two 16-byte loads), all wave-uniform
+// scalar loads through the constant address space (no store of the call may
+// touch the tables) issued a packet ahead. The header's sums are arithmetic on the
 // record; when the payload's class sums are known the header's 20 + H bytes are
 // encoded with both fields in place and stored last, once: lane J < 11 owns
 // destination dword J of the packet (source dwords J - 1 and J, the neighbour's
@@ -3276,37 +3327,9 @@ __global__ __launch_bounds__(256) void k_build(const uint8_t *payload, const uin
     yu::iov_walk_view(W, addr, plen, false, 0u);
     const uint32_t L = W.off - (yu::kBuildIp + H);  // the bytes taken: T <= 65535
 
-    uint32_t accA = 0, accB = 0;
-    uint32_t cprev = 0;  // lane 63: the last source dword of the slot before
-    while (!yu::iov_walk_done(W)) {
-      uint32_t info[U];
-      int32_t po[U];
-      uint4 c[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        po[u] = yu::iov_pack_po(vpk, W.w, lane);
-        yu::IovSlot S;
-        yu::iov_walk_slot(W, S);
-        info[u] = S.info;
-        c[u] = iov_slot_load<NT>(S, lane, u);
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        if (yu::iov_lim(info[u]) == 0) continue;  // an empty slot (wave-uniform)
-        const uint32_t t = iov_slot_sum(c[u], info[u], lane);
-        const bool swap = (info[u] & yu::kIovSwap) != 0;
-        yu::IovPackPlan P;
-        yu::iov_pack_plan(P, info[u], D, po[u], lane);
-        const uint32_t prev = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(4u * ((lane - 1u) & 63u)),
-                                                                     (int)(lead ? cprev : c[u].w));
-        yu::iov_pack_lane(st, P, lane, c[u].x, c[u].y, c[u].z, c[u].w, prev, -1, -1);
-        cprev = c[u].w;
-        accA += swap ? t : 0u;
-        accB += swap ? 0u : t;
-      }
-    }
-    const uint32_t sA = (uint32_t)__builtin_amdgcn_readlane((int)group_total<64>(accA), 63);
-    const uint32_t sB = (uint32_t)__builtin_amdgcn_readlane((int)group_total<64>(accB), 63);
+    const uint2 acc = range_walk<U, NT>(W, vpk, D, st, lane, lead);
+    const uint32_t sA = (uint32_t)__builtin_amdgcn_readlane((int)group_total<64>(acc.x), 63);
+    const uint32_t sB = (uint32_t)__builtin_amdgcn_readlane((int)group_total<64>(acc.y), 63);
     uint32_t ipsum, xsum;
     yu::build_values(R, H, L, sA, sB, ipsum, xsum);
 
@@ -3338,15 +3361,14 @@ __global__ __launch_bounds__(256) void k_build(const uint8_t *payload, const uin
 // into packet dword k in lane k. The parse, the record and the reference's
 // delivery tests read those lanes with v_readlane; the IPv4 header, the pseudo
 // header's addresses and the H fixed transport bytes are summed from them.
-// The payload [HL + H, TL) is the only thing walked: U 1-KiB slots a step,
-// each summed (k_iov's slot sum) and stored through yucsum_iov_pack.h's plan,
-// shift and masked stores with nothing held back. A packet that does not split
-// is walked for its sum alone (no room: no store). The control data of a
-// packet, its offsets pair and its pay_offsets pair, are wave-uniform scalar
-// loads through the constant address space (no store of the call may touch the
-// tables, which may be one array) issued two packets ahead, so that the header
-// load of the next packet can be issued before the current one is walked. The
-// record is stored by lanes 0..7, pay_len and out by the lead lane.
+// The payload [HL + H, TL) is the only thing walked, by range_walk. A packet
+// that does not split is walked for its sum alone (no room: no store). The
+// control data of a packet, its offsets pair and its pay_offsets pair, are
+// wave-uniform scalar loads through the constant address space (no store of
+// the call may touch the tables, which may be one array) issued two packets
+// ahead, so that the header load of the next packet can be issued before the
+// current one is walked. The record is stored by lanes 0..7, pay_len and out
+// by the lead lane.
 // ---------------------------------------------------------------------
 struct SplitArgs {
   uint8_t *pay;
@@ -3426,36 +3448,8 @@ __global__ __launch_bounds__(256) void k_split(const uint8_t *data, const uint64
     const yu::IovPackDst D = yu::split_dst(S, (uint64_t)(uintptr_t)A.pay, cur.p0, cur.p1, pN);
     yu::IovWalk W;
     const int32_t vpk = yu::split_walk(W, S, addr);
-    uint32_t accA = 0, accB = 0;
-    uint32_t cprev = 0;  // lane 63: the last source dword of the slot before
-    while (!yu::iov_walk_done(W)) {
-      uint32_t info[U];
-      int32_t po[U];
-      uint4 c[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        po[u] = yu::iov_pack_po(vpk, W.w, lane);
-        yu::IovSlot Sl;
-        yu::iov_walk_slot(W, Sl);
-        info[u] = Sl.info;
-        c[u] = iov_slot_load<NT>(Sl, lane, u);
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        if (yu::iov_lim(info[u]) == 0) continue;  // an empty slot (wave-uniform)
-        const uint32_t t = iov_slot_sum(c[u], info[u], lane);
-        const bool swap = (info[u] & yu::kIovSwap) != 0;
-        yu::IovPackPlan P;
-        yu::iov_pack_plan(P, info[u], D, po[u], lane);
-        const uint32_t prev = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(4u * ((lane - 1u) & 63u)),
-                                                                     (int)(lead ? cprev : c[u].w));
-        yu::iov_pack_lane(st, P, lane, c[u].x, c[u].y, c[u].z, c[u].w, prev, -1, -1);
-        cprev = c[u].w;
-        accA += swap ? t : 0u;
-        accB += swap ? 0u : t;
-      }
-    }
-    const uint32_t sA = group_total<64>(accA), sB = group_total<64>(accB);
+    const uint2 acc = range_walk<U, NT>(W, vpk, D, st, lane, lead);
+    const uint32_t sA = group_total<64>(acc.x), sB = group_total<64>(acc.y);
     if (lead) {
       A.out[p] = (uint16_t)yu::split_value(S, len, hs, xs, sA, sB);
       A.pay_len[p] = S.L;
@@ -3639,21 +3633,24 @@ int batch_ragged(const uint8_t *data, uint8_t *fill, const uint64_t *offsets,
 // The wave-per-packet kernels: one row per entry of YU_WAVE_KERNELS
 // (yucsum_plan.h), by load policy, from each family's template arguments. The
 // signatures differ (the packing forms add dst and dst_offsets, the datagram
-// packing form takes no side arrays, k_build its own tables), so a row fills the
-// member of its signature and leaves the others null.
+// packing form takes no side arrays, k_build and k_split their own tables), so a
+// row fills the member of its signature and leaves the others null.
 struct WaveFns {
   void (*iov[3])(const yu_iovec *, const uint64_t *, const uint16_t *, const uint8_t *, IovArgs);
   void (*pack[3])(const yu_iovec *, const uint64_t *, const uint16_t *, const uint8_t *, PackArgs);
   void (*pack_dg[3])(const yu_iovec *, const uint64_t *, PackArgs);
   void (*build[3])(const uint8_t *, const uint64_t *, const yu_tx_record *, BuildArgs);
+  void (*split[3])(const uint8_t *, const uint64_t *, SplitArgs);
 };
 #define YU_WFNS_Iov(U, FILL, DG) \
-  {{k_iov<U, 0, FILL, DG>, k_iov<U, 1, FILL, DG>, k_iov<U, 2, FILL, DG>}, {}, {}, {}}
-#define YU_WFNS_Pack_false(U, FILL) {{}, {k_pack<U, 0, FILL>, k_pack<U, 1, FILL>, k_pack<U, 2, FILL>}, {}, {}}
+  {{k_iov<U, 0, FILL, DG>, k_iov<U, 1, FILL, DG>, k_iov<U, 2, FILL, DG>}, {}, {}, {}, {}}
+#define YU_WFNS_Pack_false(U, FILL) \
+  {{}, {k_pack<U, 0, FILL>, k_pack<U, 1, FILL>, k_pack<U, 2, FILL>}, {}, {}, {}}
 #define YU_WFNS_Pack_true(U, FILL) \
-  {{}, {}, {k_pack_dg<U, 0, FILL>, k_pack_dg<U, 1, FILL>, k_pack_dg<U, 2, FILL>}, {}}
+  {{}, {}, {k_pack_dg<U, 0, FILL>, k_pack_dg<U, 1, FILL>, k_pack_dg<U, 2, FILL>}, {}, {}}
 #define YU_WFNS_Pack(U, FILL, DG) YU_WFNS_Pack_##DG(U, FILL)
-#define YU_WFNS_Build(U) {{}, {}, {}, {k_build<U, 0>, k_build<U, 1>, k_build<U, 2>}}
+#define YU_WFNS_Build(U) {{}, {}, {}, {k_build<U, 0>, k_build<U, 1>, k_build<U, 2>}, {}}
+#define YU_WFNS_Split(U) {{}, {}, {}, {}, {k_split<U, 0>, k_split<U, 1>, k_split<U, 2>}}
 #define YU_X(id, name, family, dg, fill, targs) YU_WFNS_##family targs,
 const WaveFns kWaveFns[] = {YU_WAVE_KERNELS(YU_X)};
 #undef YU_X
@@ -3770,12 +3767,7 @@ int tx_build(const uint8_t *payload, const uint64_t *pay_offsets, const yu_tx_re
   return launch_wave(&WaveFns::build, yu::WaveFamily::Build, n, 0, false, stream, payload, pay_offsets, recs, a);
 }
 
-// yu_rx_split_ragged: k_split by load policy. It is not a row of kWaveFns: no
-// family of YU_WAVE_KERNELS asks for it, and yu::plan_split plans it with the
-// same grid arithmetic (yucsum_plan.h).
-void (*const kSplitFns[3])(const uint8_t *, const uint64_t *, SplitArgs) = {k_split<4, 0>, k_split<4, 1>,
-                                                                            k_split<4, 2>};
-
+// yu_rx_split_ragged: its arguments, then the device's plan and the launch.
 int rx_split(const uint8_t *data, const uint64_t *offsets, uint64_t n, uint8_t *pay, const uint64_t *pay_offsets,
              yu_tx_record *recs, uint32_t *pay_len, uint16_t *out, void *stream) {
   if (!aligned(out, 2) || !aligned(pay_len, 4)) return YU_EINVAL;  // EINVAL:side-align
@@ -3784,13 +3776,8 @@ int rx_split(const uint8_t *data, const uint64_t *offsets, uint64_t n, uint8_t *
   if (!offsets || !aligned(offsets, 8) || !pay_offsets || !aligned(pay_offsets, 8) || !aligned(recs, 8))
     return YU_EINVAL;  // EINVAL:offsets
   if (!data || !pay || !recs || !pay_len) return YU_EINVAL;  // EINVAL:data
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return hip_status(e);
-  const yu::SplitPlan p = yu::plan_split(n, cu_count(dev), yu::env_knobs());
   const SplitArgs a = {pay, pay_offsets, (uint32_t *)recs, pay_len, out, n};
-  hipLaunchKernelGGL(kSplitFns[p.policy], dim3(p.blocks), dim3(256), 0, (hipStream_t)stream, data, offsets, a);
-  return hip_status(hipGetLastError());
+  return launch_wave(&WaveFns::split, yu::WaveFamily::Split, n, 0, false, stream, data, offsets, a);
 }
 
 // Completion signal for the host path's direct mode (yucsum_internal.h):
@@ -3931,7 +3918,7 @@ int yu_rx_split_ragged(const uint8_t *data, const uint64_t *offsets, uint64_t n,
 }
 
 const char *yu_rx_split_variant_n(uint64_t n) {
-  return yu::plan_split(n, 256, yu::env_knobs()).name;
+  return yu::plan_wave(yu::WaveFamily::Split, n, 0, false, 256, yu::env_knobs()).name;
 }
 
 const char *yu_uniform_variant(uint64_t stride, uint32_t len, int mode,

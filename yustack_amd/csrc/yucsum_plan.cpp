@@ -283,22 +283,10 @@ Plan plan(const Shape &s, int cus, const Knobs &k) {
   return p;
 }
 
-namespace {
-// The policy and the grid of a wave-per-packet launch (plan_wave, plan_split).
-void wave_grid(uint64_t n, int cus, const Knobs &k, uint8_t &policy, uint32_t &blocks_out) {
-  policy = (uint8_t)(k.nt >= 0 ? k.nt : 2);
-  const uint64_t cap = (uint64_t)cus * (k.blocks_per_cu ? k.blocks_per_cu : 64u);
-  uint64_t blocks = (n + 3) / 4;  // 4 waves per block, a wave per packet
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  blocks_out = (uint32_t)blocks;
-}
-}  // namespace
-
 // The wave-per-packet kernels: a wave per packet, four per block, on the over-
 // subscribed grid of the other wave-per-packet kernels (64 blocks per CU,
 // YU_BLOCKS_PER_CU overrides); the load policy is YU_NT's, else slot 2 (k_pack's
-// source side is k_iov's, and k_build reads its payload once). `mode` picks the
+// source side is k_iov's, and k_build and k_split read each packet once). `mode` picks the
 // kind: the whole-packet sums share one kernel, the modes that parse an IPv4 header
 // out of the packet (IPV4, VERIFY_IPV4, VERIFY_RX, TX_DATAGRAM) take the dg one;
 // the grid is the same.
@@ -313,23 +301,20 @@ WavePlan plan_wave(WaveFamily family, uint64_t n, int mode, bool fill, int cus, 
       YU_WAVE_KERNELS(YU_X)
 #undef YU_X
   };
-  const bool build = family == WaveFamily::Build;
-  const bool dg = !build && iov_dg_mode_ok(mode);
-  fill = fill && !build;
+  const bool single = family == WaveFamily::Build || family == WaveFamily::Split;  // one kernel: no kinds
+  const bool dg = !single && iov_dg_mode_ok(mode);
+  fill = fill && !single;
   int id = 0;  // every (family, dg, fill) a call can ask for has its row
   while (rows[id].family != family || rows[id].dg != dg || rows[id].fill != fill) ++id;
   WavePlan p;
   p.kernel = (WaveKernel)id;
   p.name = rows[id].name;
-  wave_grid(n, cus, k, p.policy, p.blocks);
-  return p;
-}
-
-// k_split: the same grid and policy (it reads each packet once, as k_build does).
-SplitPlan plan_split(uint64_t n, int cus, const Knobs &k) {
-  SplitPlan p;
-  p.name = "k_split<4>";
-  wave_grid(n, cus, k, p.policy, p.blocks);
+  p.policy = (uint8_t)(k.nt >= 0 ? k.nt : 2);
+  const uint64_t cap = (uint64_t)cus * (k.blocks_per_cu ? k.blocks_per_cu : 64u);
+  uint64_t blocks = (n + 3) / 4;  // 4 waves per block, a wave per packet
+  if (blocks > cap) blocks = cap;
+  if (blocks < 1) blocks = 1;
+  p.blocks = (uint32_t)blocks;
   return p;
 }
 

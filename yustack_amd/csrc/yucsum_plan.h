@@ -2,8 +2,9 @@
 // which load policy and on which grid. One list of kernels (YU_KERNELS) and one
 // pure function (plan) hold the whole decision; yucsum_kernels.hip builds its
 // function table from the same list and launches what the plan names. The
-// wave-per-packet calls (scatter-gather, packing, yu_tx_build_ragged) have the
-// same pair beside it: YU_WAVE_KERNELS and plan_wave. No HIP call is made here,
+// wave-per-packet calls (scatter-gather, packing, yu_tx_build_ragged,
+// yu_rx_split_ragged) have the same pair beside it: YU_WAVE_KERNELS and
+// plan_wave. No HIP call is made here,
 // so tests/cpp/plan_table.cpp and tests/cpp/wave_plan.cpp check every decision
 // on a CPU.
 #ifndef YUCSUM_PLAN_H
@@ -178,8 +179,9 @@ Plan plan(const Shape &s, int cus, const Knobs &k);
 
 // The wave-per-packet device calls have a list and a plan of their own: the
 // scatter-gather sums (k_iov, yucsum_iov.h), their packing form (k_pack, k_pack_dg:
-// yucsum_iov_pack.h) and yu_tx_build_ragged (k_build, yucsum_build.h). None is one
-// of YU_KERNELS, because no uniform or ragged batch ever takes them. Each once:
+// yucsum_iov_pack.h), yu_tx_build_ragged (k_build, yucsum_build.h) and
+// yu_rx_split_ragged (k_split, yucsum_split.h). None is one of YU_KERNELS, because
+// no uniform or ragged batch ever takes them. Each once:
 // X(id, name, family, dg, fill, targs).
 //   dg     the kind for whole IPv4 datagrams (the modes of yu::iov_dg_mode_ok)
 //   fill   the instantiation that stores the checksum fields
@@ -194,9 +196,10 @@ Plan plan(const Shape &s, int cus, const Knobs &k);
   X(pack4_fill, "k_pack<4,fill>", Pack, false, true, (4, true, false))              \
   X(pack4_dg, "k_pack<4,dg>", Pack, true, false, (4, false, true))                  \
   X(pack4_dg_fill, "k_pack<4,dg,fill>", Pack, true, true, (4, true, true))          \
-  X(build4, "k_build<4>", Build, false, false, (4))
+  X(build4, "k_build<4>", Build, false, false, (4))                                \
+  X(split4, "k_split<4>", Split, false, false, (4))
 
-enum class WaveFamily : uint8_t { Iov, Pack, Build };
+enum class WaveFamily : uint8_t { Iov, Pack, Build, Split };
 enum WaveKernel : uint8_t {
 #define YU_X(id, ...) k_##id,
   YU_WAVE_KERNELS(YU_X)
@@ -207,23 +210,12 @@ struct WavePlan {
   WaveKernel kernel;
   uint8_t policy;  // load-policy slot: 0 plain, 1 nt, 2 plain for a step's first slot, nt for the rest
   uint32_t blocks;
-  const char *name;  // what the yu_iov*_variant_n calls and yu_tx_build_variant_n return
+  const char *name;  // what the yu_*_variant_n calls of these families return
 };
 // Iov, Pack: any mode; one of the whole-datagram modes (yu::iov_dg_mode_ok) picks
-// the dg kernels, every other the whole-packet ones. Build: mode and fill are ignored.
+// the dg kernels, every other the whole-packet ones. Build, Split: one kernel each,
+// mode and fill are ignored.
 WavePlan plan_wave(WaveFamily family, uint64_t n, int mode, bool fill, int cus, const Knobs &k);
-
-// yu_rx_split_ragged (k_split, yucsum_split.h) has one kernel and a plan beside
-// plan_wave, not a tenth row of YU_WAVE_KERNELS: the table's rows are what a
-// (family, dg, fill) of the scatter-gather, packing and building calls resolves
-// to, and no such call ever resolves to k_split. The policy and the grid are
-// plan_wave's own arithmetic, one copy of it.
-struct SplitPlan {
-  uint8_t policy;  // as WavePlan's
-  uint32_t blocks;
-  const char *name;  // what yu_rx_split_variant_n returns
-};
-SplitPlan plan_split(uint64_t n, int cus, const Knobs &k);
 
 }  // namespace yu
 #pragma GCC visibility pop
