@@ -73,8 +73,8 @@ extern "C" {
 /*                  parse headers out of the packet; the whole-datagram  */
 /*                  calls (yu_csum_*_iov_datagram) take those four and   */
 /*                  refuse every other mode.                             */
-/*  [out]           out == NULL in a yu_csum_batch_* call or in          */
-/*                  yu_rx_split_ragged, or h_out ==                      */
+/*  [out]           out == NULL in a yu_csum_batch_* call, in            */
+/*                  yu_rx_split_ragged or in yu_rx_parse_ragged, or h_out == */
 /*                  NULL in a yu_csum_batch_host_* call, with n > 0 (the */
 /*                  fill calls take NULL: no result array; an empty     */
 /*                  batch, n == 0, is a no-op returning YU_OK).          */
@@ -86,14 +86,17 @@ extern "C" {
 /*  [side-align]    device calls: initial_arr not 2-byte aligned, addrs  */
 /*                  not 4-byte aligned, out not 2-byte aligned           */
 /*                  (yu_tx_build_ragged: out; yu_rx_split_ragged: out,   */
-/*                  and pay_len not 4-byte aligned).                     */
+/*                  and pay_len not 4-byte aligned; yu_rx_parse_ragged:  */
+/*                  out).                                                */
 /*  [data]          data == NULL with n > 0 (device calls), h_data ==    */
 /*                  NULL while the packets hold bytes (host calls), iov  */
 /*                  == NULL while first_iov names views; views == NULL  */
 /*                  with n > 0 (yu_csum_*_iov); dst == NULL with n > 0   */
 /*                  (yu_csum_pack_*_iov); payload, recs or dst == NULL   */
 /*                  with n > 0 (yu_tx_build_ragged); data, pay, recs or  */
-/*                  pay_len == NULL with n > 0 (yu_rx_split_ragged).     */
+/*                  pay_len == NULL with n > 0 (yu_rx_split_ragged);     */
+/*                  data, recs or pay_views == NULL with n > 0           */
+/*                  (yu_rx_parse_ragged).                                */
 /*  [len-transport] a packet of a mode other than RAW longer than        */
 /*                  YU_MAX_TRANSPORT_LEN (uniform len; every host ragged */
 /*                  or iov packet). Device ragged batches are not read   */
@@ -112,7 +115,9 @@ extern "C" {
 /*                  dst_offsets == NULL or not 8-byte aligned, recs not  */
 /*                  8-byte aligned; yu_rx_split_ragged: offsets or       */
 /*                  pay_offsets == NULL or not 8-byte aligned, recs not  */
-/*                  8-byte aligned.                                      */
+/*                  8-byte aligned; yu_rx_parse_ragged: offsets == NULL  */
+/*                  or not 8-byte aligned, recs or pay_views not 8-byte  */
+/*                  aligned.                                             */
 /*  [iov-view]    a view with base == NULL and len > 0.                */
 /*  [fill-align]    yu_csum_fill_uniform: data or stride not a multiple  */
 /*                  of 4. The uniform writers store whole dwords of each */
@@ -279,7 +284,7 @@ uint16_t yu_pseudo_header_checksum(uint32_t protocol,
 #define YU_RX_L4 2u      /* transport (TCP/UDP/ICMP) present and checked */
 #define YU_RX_L4_OK 4u   /* transport checksum verifies */
 #define YU_RX_INVALID 8u /* IPv4.IsValid fails (nothing else is set) */
-#define YU_RX_SPLIT 16u  /* yu_rx_split_ragged only: record, pay_len and payload of this packet are defined */
+#define YU_RX_SPLIT 16u  /* yu_rx_split_ragged, yu_rx_parse_ragged: record and payload (pay_len, or the view) of this packet are defined */
 
 /* Packets handed to the transport/IPv4/ICMP modes must be <= 65535 bytes
  * (the IPv4 total-length limit; the reference's uint16 length arithmetic is
@@ -778,6 +783,61 @@ int yu_rx_split_ragged(const uint8_t *data, const uint64_t *offsets, uint64_t n,
                        yu_tx_record *recs, uint32_t *pay_len,
                        uint16_t *out, void *stream);
 
+/* Received IPv4 datagrams parsed where they lie: yu_rx_split_ragged without the
+ * payload copy, for a receiver that runs its state machine on the records and
+ * consumes, gathers or drops the payloads later, or needs the headers only.
+ * Instead of a copied payload and pay_len it stores one yu_iovec per packet that
+ * points at the payload inside `data`.
+ *
+ * Call discipline: that of yu_rx_split_ragged, word for word. Every pointer is a
+ * DEVICE pointer; asynchronous on `stream`, no allocation, no synchronisation,
+ * graph-capturable, YU_ENODEV without a device, n == 0 a no-op returning YU_OK
+ * after the checks that do not need n. Input: the ragged batch
+ * yu_csum_batch_ragged takes (n + 1 DEVICE uint64 offsets, 8-byte aligned), at
+ * any byte alignment.
+ *
+ * Per packet, with b, len, HL, TL, P, S, slen, H and L as for
+ * yu_rx_split_ragged:
+ *   recs[i]       exactly the record yu_rx_split_ragged stores: the header fields
+ *                 with YU_RX_SPLIT, 32 zero bytes without it.
+ *   pay_views[i]  with YU_RX_SPLIT {base = data + offsets[i] + HL + H, len = L},
+ *                 the bytes yu_rx_split_ragged would have copied; without it
+ *                 {NULL, 0}. n DEVICE yu_iovec, 8-byte aligned. With first_iov =
+ *                 0, 1, .., n it is a view table the yu_csum_*_iov calls take as
+ *                 it is, so "parse, decide, gather what was accepted" is this
+ *                 call, the caller's decision and yu_csum_pack_iov.
+ *   out[i]        verify != 0: exactly yu_rx_split_ragged's value, VERIFY_RX's
+ *                 four bits plus YU_RX_SPLIT. verify == 0: that value &
+ *                 (YU_RX_INVALID | YU_RX_SPLIT), the two bits the header alone
+ *                 decides; no checksum is computed and no payload byte is read.
+ *
+ * Launches: with verify != 0 the VERIFY_RX launch of yu_csum_batch_ragged
+ * (yu_ragged_variant_n(YU_MODE_VERIFY_RX, n) names its kernel), which stores
+ * out, then the header pass (yu_rx_parse_variant_n) on the same stream, in which
+ * the lane that owns packet i ORs YU_RX_SPLIT into out[i]. With verify == 0 the
+ * header pass alone.
+ *
+ * Stores and reads: every record, every view and every out is stored by the call
+ * (nothing needs pre-clearing); nothing else is written, `data` never. Reads lie
+ * in the dwords holding data[0, offsets[n]); with verify == 0 only dwords holding
+ * bytes of each packet's first min(len, 80) bytes are read.
+ *
+ * Out of contract (the tables are device memory and are not read on the host): a
+ * packet at which offsets decreases, one longer than YU_MAX_TRANSPORT_LEN or one
+ * ending past offsets[n] gets an unspecified record, view and out of its own,
+ * never a fault or a hang. The record, the view and the YU_RX_SPLIT bit of every
+ * other packet are exact (the header pass takes each packet by itself); the four
+ * VERIFY_RX bits follow yu_csum_batch_ragged's group rule ("Out of contract"
+ * above).
+ *
+ * YU_EINVAL (Preconditions above): [data]: data, recs or pay_views NULL with
+ * n > 0; [out]: out NULL with n > 0; [offsets]: offsets NULL or not 8-byte
+ * aligned, recs or pay_views not 8-byte aligned; [side-align]: out not 2-byte
+ * aligned (checked without n). */
+int yu_rx_parse_ragged(const uint8_t *data, const uint64_t *offsets, uint64_t n,
+                       int verify, yu_tx_record *recs, yu_iovec *pay_views,
+                       uint16_t *out, void *stream);
+
 /* Host-memory field writer: the matching yu_csum_batch_host_* call (TX modes
  * UDP/TCP/IPV4/ICMP/TX_DATAGRAM only), then each result stored big-endian into the
  * packet's checksum field in host memory, as the device writer does
@@ -921,6 +981,8 @@ const char *yu_iov_pack_datagram_variant_n(int mode, uint64_t n, int fill);
 const char *yu_tx_build_variant_n(uint64_t n);
 /* The same for yu_rx_split_ragged. */
 const char *yu_rx_split_variant_n(uint64_t n);
+/* The header pass of yu_rx_parse_ragged ("k_parse"). No device needed. */
+const char *yu_rx_parse_variant_n(uint64_t n);
 
 #ifdef __cplusplus
 }

@@ -37,6 +37,8 @@ PROTOTYPES = {
     "yu_tx_build_ragged": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     # data, offsets, n, pay, pay_offsets, recs, pay_len, out, stream
     "yu_rx_split_ragged": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # data, offsets, n, verify, recs, pay_views, out, stream
+    "yu_rx_parse_ragged": (_i32, [_vp, _vp, _u64, _i32, _vp, _vp, _vp, _vp]),
     **_same("yu_csum_batch_host_uniform yu_csum_fill_host_uniform", _i32, _UNIFORM + [_i32]),  # + device
     **_same("yu_csum_batch_host_ragged yu_csum_fill_host_ragged yu_csum_batch_host_iov yu_csum_fill_host_iov", _i32,
             _RAGGED + [_i32]),
@@ -51,7 +53,7 @@ PROTOTYPES = {
     **_same("yu_ragged_variant_n yu_ragged_fill_variant_n", _str, [_i32, _u64]),
     **_same("yu_iov_variant_n yu_iov_datagram_variant_n yu_iov_pack_variant_n yu_iov_pack_datagram_variant_n", _str,
             [_i32, _u64, _i32]),
-    **_same("yu_tx_build_variant_n yu_rx_split_variant_n", _str, [_u64]),
+    **_same("yu_tx_build_variant_n yu_rx_split_variant_n yu_rx_parse_variant_n", _str, [_u64]),
     "yu_host_contexts": (_i32, []),
     "yu_host_staging_bytes": (_u64, [_i32, _vp]),
     "yu_host_staging_trim": (_i32, [_i32]),

@@ -588,6 +588,90 @@ def split_datagrams(data: torch.Tensor, offsets: torch.Tensor, *, pay: torch.Ten
     return pay, (offsets if pay_offsets is None else pay_offsets), pay_len, records, out
 
 
+def parse_datagrams(data: torch.Tensor, offsets: torch.Tensor, *, verify: bool = True,
+                    records: torch.Tensor | None = None, views: torch.Tensor | None = None,
+                    out: torch.Tensor | None = None, validate: bool = False,
+                    stream: torch.cuda.Stream | None = None):
+    """Received IPv4 datagrams parsed where they lie (yu_rx_parse_ragged):
+    :func:`split_datagrams` without the payload copy. Packet i is ``data[offsets[i] :
+    offsets[i+1]]`` (n+1 int64/uint64 offsets). Returns ``(records, views, out)``:
+    ``records`` (shape (n, 32) uint8) are :func:`split_datagrams`'s; ``views`` (shape
+    (n, 2) int64) holds, where :data:`RX_SPLIT` is set, the payload's device address and
+    its length L, and ``(0, 0)`` where it is not; ``out[i]`` is :func:`split_datagrams`'s
+    value with ``verify=True`` (``verify_rx``'s flags plus :data:`RX_SPLIT`, two launches)
+    and that value ``& (RX_INVALID | RX_SPLIT)`` with ``verify=False`` (the header pass
+    alone: no checksum is computed and no payload byte is read).
+
+    The payloads stay in ``data``: ``views[:, 0] - data.data_ptr()`` and ``views[:, 1]``
+    are the ``view_off`` and ``view_len`` that ``batch.pack_iov([data], view_pool, view_off,
+    view_len, first, ...)`` takes (``view_pool`` zeros, ``first = arange(n + 1)``, or fewer
+    rows for the packets the receiver accepts), so gathering what was accepted is a
+    composition of the two calls. In C the table is a ``yu_iovec`` array as it is.
+
+    ``validate=True`` reads the offsets back and raises ValueError where they are out of
+    the call's contract (include/yucsum.h). With every tensor given the call is capturable
+    in a graph."""
+    _dev_u8(data, "data")
+    dev = data.device
+    if not isinstance(offsets, torch.Tensor) or not offsets.is_cuda or offsets.device != dev:
+        raise TypeError(f"offsets must be a CUDA tensor on {dev}")
+    if offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError("offsets must hold n + 1 entries")
+    n = offsets.numel() - 1
+    o = _dev_index(offsets, "offsets", dev, n + 1)
+    if o.data_ptr() % 8:
+        raise TypeError("offsets must be 8-byte aligned")
+    if records is None:
+        records = torch.empty((max(n, 1), 32), dtype=torch.uint8, device=dev)[:n]
+    else:
+        _dev_u8(records, "records")
+        if records.device != dev:
+            raise TypeError(f"records must be on {dev}")
+        if records.dim() != 2 or records.shape != (n, 32):
+            raise ValueError("records must have shape (n, 32)")
+        if records.data_ptr() % 8:
+            raise TypeError("records must be 8-byte aligned")
+        if _overlaps(records, data):
+            raise ValueError("records overlaps data")
+    if views is None:
+        views = torch.empty((max(n, 1), 2), dtype=torch.int64, device=dev)[:n]
+    else:
+        if not isinstance(views, torch.Tensor) or not views.is_cuda or views.device != dev:
+            raise TypeError(f"views must be a CUDA tensor on {dev}")
+        if views.dtype != torch.int64 or not views.is_contiguous():
+            raise TypeError("views must be a contiguous int64 tensor")
+        if views.dim() != 2 or views.shape != (n, 2):
+            raise ValueError("views must have shape (n, 2)")
+        if _overlaps(views, data) or _overlaps(views, records):
+            raise ValueError("views overlaps data or records")
+    if validate and n > 0:
+        plen = o[1:] - o[:-1]
+        ok = torch.stack(((plen >= 0).all() & (o[0] >= 0) & (o[-1] <= data.numel()),
+                          (plen <= MAX_TRANSPORT_LEN).all())).tolist()
+        if not ok[0]:
+            raise ValueError("offsets is not non-decreasing within data")
+        if not ok[1]:
+            raise ValueError("datagrams must be <= 65535 bytes")
+    out = _result(out, n, dev)
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream(dev))
+        for t in (o, records, views, out):
+            t.record_stream(stream)
+    with torch.cuda.device(dev):
+        rc = lib().yu_rx_parse_ragged(data.data_ptr(), o.data_ptr(), n, 1 if verify else 0,
+                                      records.data_ptr() if n else None, views.data_ptr() if n else None,
+                                      out.data_ptr() if n else None, _stream(dev, stream))
+    check(rc, "yu_rx_parse_ragged")
+    out.parse_tables = (o, data)  # read asynchronously, and the views point into data: keep both alive
+    return records, views, out
+
+
+def parse_variant(n: int = 1 << 20) -> str:
+    """Name of the kernel of :func:`parse_datagrams`'s header pass for a batch of n packets
+    (with ``verify=True`` :func:`ragged_variant` ``("verify_rx", n)`` names the launch before it)."""
+    return _wave_variant("rx_parse", n)
+
+
 def split_variant(n: int = 1 << 20) -> str:
     """Name of the kernel :func:`split_datagrams` launches for a batch of n packets."""
     return _wave_variant("rx_split", n)

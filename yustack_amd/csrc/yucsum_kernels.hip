@@ -92,6 +92,10 @@
 //     record and the header sums, the payload [HL + H, TL) as a single view
 //     through k_pack's store side (yucsum_split.h). k_build and k_split walk
 //     their one range with the same function, range_walk.
+//   k_parse<VERIFY, NT>: yu_rx_parse_ragged's header pass (planned by
+//     yu::plan_parse): one lane per received datagram, k_split's record and
+//     YU_RX_SPLIT from the packet's first 80 bytes and a view onto the payload,
+//     which is neither read nor copied (yucsum_parse.h).
 //   All are grid-stride kernels; the grid is sized per CU and over-subscribed
 //   (see blocks_per_cu in yucsum_plan.cpp), except that k_seg narrows it for
 //   small packets (seg_waves).
@@ -109,6 +113,7 @@
 #include "yucsum_internal.h"
 #include "yucsum_iov.h"
 #include "yucsum_iov_pack.h"
+#include "yucsum_parse.h"
 #include "yucsum_plan.h"
 #include "yucsum_split.h"
 
@@ -3469,6 +3474,107 @@ __global__ __launch_bounds__(256) void k_split(const uint8_t *data, const uint64
 }
 
 // ---------------------------------------------------------------------
+// k_parse<VERIFY, NT>: received IPv4 datagrams parsed where they lie
+// (yu_rx_parse_ragged; yucsum_parse.h has the arithmetic): k_split's record and
+// YU_RX_SPLIT bit, and a yu_iovec onto the payload instead of a copy of it. The
+// parse, the delivery tests and the record read at most a packet's first 80
+// bytes, so this is a lane per packet, 64 packets per wave step, like k_hdr,
+// and no payload byte is touched. A lane reads its own offsets pair as ordinary
+// loads and cuts its own packet to the batch (split_src), so an out-of-contract
+// packet changes no other lane's addresses; each of its window dwords is one
+// global load, made only under parse_loads (inside the packet's own window, which
+// split_src has already cut to data[0, offsets[n])) and zero otherwise. Window
+// dwords 0 .. 9 serve IHL 5; the five past them are loaded only when some lane
+// of the step has another IHL, at window index IHL + k: a second load, never a
+// runtime index into the registers already held. The record leaves as two
+// 16-byte stores per lane and the view as one, contiguous across the lanes.
+// VERIFY: out[i] already holds VERIFY_RX's bits, stored by the launch before this
+// one on the stream; the lane that owns packet i ORs YU_RX_SPLIT into it.
+// Otherwise out[i] is stored here: YU_RX_INVALID and YU_RX_SPLIT.
+// ---------------------------------------------------------------------
+struct ParseArgs {
+  uint8_t *recs;   // yu_tx_record, 32 bytes each, 8-byte aligned
+  uint8_t *views;  // yu_iovec, 16 bytes each, 8-byte aligned
+  uint16_t *out;
+  uint64_t n;
+};
+
+// A 16-byte store to an 8-byte aligned address (the tables' contract).
+typedef uint32_t u32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));
+
+// Window loads: global memory, 4-byte aligned, one, two or four dwords.
+typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+#define YU_GLOBAL_AS __attribute__((address_space(1)))
+
+template <typename T, int NT>
+__device__ __forceinline__ T parse_ld(uint64_t a) {
+  const YU_GLOBAL_AS T *p = (const YU_GLOBAL_AS T *)(uintptr_t)a;
+  return NT ? __builtin_nontemporal_load(p) : *p;
+}
+
+template <bool VERIFY, int NT>
+__global__ __launch_bounds__(256) void k_parse(const uint8_t *data, const uint64_t *offsets, ParseArgs A) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t wave = grid_wave(0u);
+  const uint64_t nwave = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  const uint64_t oN = offsets[A.n];
+  for (uint64_t p0 = wave * yu::kParsePerWave; p0 < A.n; p0 += nwave * yu::kParsePerWave) {
+    const uint64_t p = p0 + lane;
+    const bool act = p < A.n;  // lanes past the batch: an empty packet, nothing is loaded
+    const uint64_t o0 = offsets[act ? p : A.n], o1 = offsets[act ? p + 1 : A.n];
+    uint32_t flags = 0;
+    if (VERIFY && act) flags = A.out[p];
+    uint64_t addr;
+    uint32_t len;
+    yu::split_src((uint64_t)(uintptr_t)data, o0, o1, oN, addr, len);
+    const uint32_t lim = yu::split_hdr_lim(addr, len), s = (uint32_t)addr & 3u;
+    const uint64_t base = addr & ~3ull;
+    uint32_t w[yu::kParseFix];
+    if (yu::parse_whole(lim)) {  // all ten: 16 + 16 + 8 bytes
+      static_assert(yu::kParseFix == 10u, "window dwords 0 .. 9 as three loads");
+      const u32x4_a4 a = parse_ld<u32x4_a4, NT>(base), b = parse_ld<u32x4_a4, NT>(base + 16u);
+      const u32x2_a4 c = parse_ld<u32x2_a4, NT>(base + 32u);
+      w[0] = a.x, w[1] = a.y, w[2] = a.z, w[3] = a.w;
+      w[4] = b.x, w[5] = b.y, w[6] = b.z, w[7] = b.w;
+      w[8] = c.x, w[9] = c.y;
+    } else {
+#pragma unroll
+      for (uint32_t j = 0; j < yu::kParseFix; ++j)
+        w[j] = yu::parse_loads(j, lim) ? parse_ld<uint32_t, NT>(base + 4u * j) : 0u;
+    }
+    yu::ParseHdr H;
+    yu::parse_fixed(H, w, s);
+    const bool opt = yu::parse_needs_opt(H, len);
+    if (__any((int)opt)) {
+      uint32_t x[yu::kParseOpt];
+#pragma unroll
+      for (uint32_t k = 0; k < yu::kParseOpt; ++k) {
+        const uint32_t j = yu::parse_opt_dword(H, k);
+        x[k] = opt && yu::parse_loads(j, lim) ? parse_ld<uint32_t, NT>(base + 4u * j) : 0u;
+      }
+      if (opt) yu::parse_opt(H, x, s);
+    }
+    yu::SplitDg S;
+    yu::split_parse(S, len, H.d0, H.d2, H.t1, H.t3);
+    yu::BuildRec R;
+    yu::split_record(R, S, H.d0, H.d1, H.d2, H.d3, H.d4, H.t0, H.t1, H.t2, H.t3);
+    const yu::ParseView V = yu::parse_view(S, addr);
+    const uint32_t bits = yu::parse_hdr_bits(S, len);
+    if (act) {
+      u32x4_a8 r0, r1, v;
+      r0.x = R.w[0], r0.y = R.w[1], r0.z = R.w[2], r0.w = R.w[3];
+      r1.x = R.w[4], r1.y = R.w[5], r1.z = R.w[6], r1.w = R.w[7];
+      v.x = (uint32_t)V.base, v.y = (uint32_t)(V.base >> 32), v.z = (uint32_t)V.len, v.w = (uint32_t)(V.len >> 32);
+      *(u32x4_a8 *)(A.recs + 32u * p) = r0;
+      *(u32x4_a8 *)(A.recs + 32u * p + 16u) = r1;
+      *(u32x4_a8 *)(A.views + 16u * p) = v;
+      A.out[p] = (uint16_t)(VERIFY ? (flags | (bits & yu::kSplitFlag)) : bits);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------
 // Host side: launch. Which kernel, form, load policy and grid a batch gets is
 // yu::plan's decision (yucsum_plan.cpp); here are the functions it names.
 // ---------------------------------------------------------------------
@@ -3780,6 +3886,33 @@ int rx_split(const uint8_t *data, const uint64_t *offsets, uint64_t n, uint8_t *
   return launch_wave(&WaveFns::split, yu::WaveFamily::Split, n, 0, false, stream, data, offsets, a);
 }
 
+// yu_rx_parse_ragged: its arguments; with `verify` the VERIFY_RX launch exactly as
+// yu_csum_batch_ragged makes it (yu::plan's kernel, which stores out), then
+// k_parse on yu::plan_parse's grid, on the same stream.
+int rx_parse(const uint8_t *data, const uint64_t *offsets, uint64_t n, int verify, yu_tx_record *recs,
+             yu_iovec *pay_views, uint16_t *out, void *stream) {
+  if (!aligned(out, 2)) return YU_EINVAL;  // EINVAL:side-align
+  if (n == 0) return YU_OK;
+  if (!out) return YU_EINVAL;  // EINVAL:out
+  if (!offsets || !aligned(offsets, 8) || !aligned(recs, 8) || !aligned(pay_views, 8))
+    return YU_EINVAL;  // EINVAL:offsets
+  if (!data || !recs || !pay_views) return YU_EINVAL;  // EINVAL:data
+  if (verify) {
+    const int rc = batch_ragged(data, nullptr, offsets, n, YU_MODE_VERIFY_RX, nullptr, 0, nullptr, out, stream);
+    if (rc != YU_OK) return rc;
+  }
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return hip_status(e);
+  const yu::ParsePlan p = yu::plan_parse(n, cu_count(dev), yu::env_knobs());
+  const ParseArgs a = {(uint8_t *)recs, (uint8_t *)pay_views, out, n};
+  void (*const fn[2][2])(const uint8_t *, const uint64_t *, ParseArgs) = {{k_parse<false, 0>, k_parse<false, 1>},
+                                                                          {k_parse<true, 0>, k_parse<true, 1>}};
+  hipLaunchKernelGGL(fn[verify ? 1 : 0][p.policy], dim3(p.blocks), dim3(256), 0, (hipStream_t)stream, data, offsets,
+                     a);
+  return hip_status(hipGetLastError());
+}
+
 // Completion signal for the host path's direct mode (yucsum_internal.h):
 // stored after the work before it on the stream, with system-scope release,
 // into coherent pinned host memory.
@@ -3919,6 +4052,15 @@ int yu_rx_split_ragged(const uint8_t *data, const uint64_t *offsets, uint64_t n,
 
 const char *yu_rx_split_variant_n(uint64_t n) {
   return yu::plan_wave(yu::WaveFamily::Split, n, 0, false, 256, yu::env_knobs()).name;
+}
+
+int yu_rx_parse_ragged(const uint8_t *data, const uint64_t *offsets, uint64_t n, int verify, yu_tx_record *recs,
+                       yu_iovec *pay_views, uint16_t *out, void *stream) {
+  return rx_parse(data, offsets, n, verify, recs, pay_views, out, stream);
+}
+
+const char *yu_rx_parse_variant_n(uint64_t n) {
+  return yu::plan_parse(n, 256, yu::env_knobs()).name;
 }
 
 const char *yu_uniform_variant(uint64_t stride, uint32_t len, int mode,

@@ -4,7 +4,8 @@
 // function table from the same list and launches what the plan names. The
 // wave-per-packet calls (scatter-gather, packing, yu_tx_build_ragged,
 // yu_rx_split_ragged) have the same pair beside it: YU_WAVE_KERNELS and
-// plan_wave. No HIP call is made here,
+// plan_wave; yu_rx_parse_ragged's header pass, a lane per packet, has plan_parse.
+// No HIP call is made here,
 // so tests/cpp/plan_table.cpp and tests/cpp/wave_plan.cpp check every decision
 // on a CPU.
 #ifndef YUCSUM_PLAN_H
@@ -216,6 +217,16 @@ struct WavePlan {
 // the dg kernels, every other the whole-packet ones. Build, Split: one kernel each,
 // mode and fill are ignored.
 WavePlan plan_wave(WaveFamily family, uint64_t n, int mode, bool fill, int cus, const Knobs &k);
+
+// yu_rx_parse_ragged's header pass (k_parse, yucsum_parse.h) is a lane per packet,
+// 64 packets per wave step, so it is a row of neither list: no uniform or ragged
+// batch takes it and it is no wave-per-packet kernel. One kernel, its plan here.
+struct ParsePlan {
+  uint8_t policy;  // load-policy slot: 0 plain, 1 nt
+  uint32_t blocks;
+  const char *name;  // what yu_rx_parse_variant_n returns
+};
+ParsePlan plan_parse(uint64_t n, int cus, const Knobs &k);
 
 }  // namespace yu
 #pragma GCC visibility pop
