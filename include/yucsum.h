@@ -74,7 +74,8 @@ extern "C" {
 /*                  calls (yu_csum_*_iov_datagram) take those four and   */
 /*                  refuse every other mode.                             */
 /*  [out]           out == NULL in a yu_csum_batch_* call, in            */
-/*                  yu_rx_split_ragged or in yu_rx_parse_ragged, or h_out == */
+/*                  yu_rx_split_ragged or in yu_rx_parse_ragged, ep == NULL */
+/*                  in yu_rx_demux, or h_out ==                          */
 /*                  NULL in a yu_csum_batch_host_* call, with n > 0 (the */
 /*                  fill calls take NULL: no result array; an empty     */
 /*                  batch, n == 0, is a no-op returning YU_OK).          */
@@ -87,7 +88,8 @@ extern "C" {
 /*                  not 4-byte aligned, out not 2-byte aligned           */
 /*                  (yu_tx_build_ragged: out; yu_rx_split_ragged: out,   */
 /*                  and pay_len not 4-byte aligned; yu_rx_parse_ragged:  */
-/*                  out).                                                */
+/*                  out; yu_rx_demux: flags not 2-byte aligned, ep or    */
+/*                  ep_count not 4-byte aligned).                        */
 /*  [data]          data == NULL with n > 0 (device calls), h_data ==    */
 /*                  NULL while the packets hold bytes (host calls), iov  */
 /*                  == NULL while first_iov names views; views == NULL  */
@@ -96,7 +98,11 @@ extern "C" {
 /*                  with n > 0 (yu_tx_build_ragged); data, pay, recs or  */
 /*                  pay_len == NULL with n > 0 (yu_rx_split_ragged);     */
 /*                  data, recs or pay_views == NULL with n > 0           */
-/*                  (yu_rx_parse_ragged).                                */
+/*                  (yu_rx_parse_ragged); recs or table == NULL with     */
+/*                  n > 0, table_bytes != yu_demux_table_bytes(m) or m > */
+/*                  YU_DEMUX_MAX_ENDPOINTS (yu_rx_demux); the same two,  */
+/*                  ids or h_table == NULL with m > 0, a malformed id or */
+/*                  one equal to an earlier id (yu_demux_table_fill).    */
 /*  [len-transport] a packet of a mode other than RAW longer than        */
 /*                  YU_MAX_TRANSPORT_LEN (uniform len; every host ragged */
 /*                  or iov packet). Device ragged batches are not read   */
@@ -117,7 +123,8 @@ extern "C" {
 /*                  pay_offsets == NULL or not 8-byte aligned, recs not  */
 /*                  8-byte aligned; yu_rx_parse_ragged: offsets == NULL  */
 /*                  or not 8-byte aligned, recs or pay_views not 8-byte  */
-/*                  aligned.                                             */
+/*                  aligned; yu_rx_demux: recs not 8-byte aligned, table */
+/*                  not 16-byte aligned.                                 */
 /*  [iov-view]    a view with base == NULL and len > 0.                */
 /*  [fill-align]    yu_csum_fill_uniform: data or stride not a multiple  */
 /*                  of 4. The uniform writers store whole dwords of each */
@@ -838,6 +845,119 @@ int yu_rx_parse_ragged(const uint8_t *data, const uint64_t *offsets, uint64_t n,
                        int verify, yu_tx_record *recs, yu_iovec *pay_views,
                        uint16_t *out, void *stream);
 
+/* Transport demultiplexing on the device: which endpoint gets a received packet.
+ * Once the ports are read, Nic.DeliverTransportPacket hands the packet to
+ * transportDemuxer.deliverPacket, whose deliverPacketLocked looks the packet's
+ * TransportEndpointId up three times, in a fixed order: the full 4-tuple (a
+ * connection), the id with the remote part emptied (a listener bound to an
+ * address), the id with the local address emptied as well (a listener on a
+ * port). The first hit gets the packet; with none the packet is dropped. The
+ * protocol is part of every key (the demuxer's first level). yu_rx_demux is that
+ * function for a batch of records as yu_rx_parse_ragged / yu_rx_split_ragged
+ * store them, against one table of registered ids. Endpoints, registration at
+ * run time, locking, routes and the state machines stay with the caller. */
+#define YU_DEMUX_NONE 0xFFFFFFFFu          /* no endpoint: the reference drops the packet */
+#define YU_DEMUX_MAX_ENDPOINTS (1u << 24)
+
+/* One registered types.TransportEndpointId plus its protocol: 16 bytes. `kind`
+ * is explicit because Go's empty Address is not 0.0.0.0: a connection from
+ * 0.0.0.0:0 and a listener are different keys. */
+typedef struct yu_endpoint_id {
+  uint8_t  local_addr[4];    /* wire bytes; zero when kind == 2                       */
+  uint8_t  remote_addr[4];   /* wire bytes; zero when kind != 0                       */
+  uint16_t local_port;       /* host byte order, as yu_tx_record's ports              */
+  uint16_t remote_port;      /* zero when kind != 0                                   */
+  uint8_t  proto;            /* 6 or 17                                               */
+  uint8_t  kind;             /* 0: all four fields (a connection)                     */
+                             /* 1: RemoteAddress "" and RemotePort 0 (listener on an address) */
+                             /* 2: LocalAddress "" as well (listener on a port)       */
+  uint16_t reserved;         /* 0 */
+} yu_endpoint_id;
+
+/* The table of m ids: an open-addressed hash table whose layout is the
+ * library's own, yu_demux_table_bytes(m) bytes (16 bytes per slot; the slot
+ * count is the power of two that is at least 16 and at least 2m). 0 when
+ * m > YU_DEMUX_MAX_ENDPOINTS. No device needed. */
+uint64_t yu_demux_table_bytes(uint64_t m);
+/* The 32-bit hash of an id as the table uses it: an id's home slot is
+ * yu_demux_hash(id) & (yu_demux_table_bytes(m) / 16 - 1), and ids with one home
+ * slot follow each other from it on, wrapping at the table's end. Exported so
+ * that colliding ids can be constructed. Fields the id's kind empties are
+ * hashed as they stand. No device needed. */
+uint32_t yu_demux_hash(const yu_endpoint_id *id);
+/* Fills the HOST buffer h_table (table_bytes == yu_demux_table_bytes(m)) with
+ * the table of ids[0, m); the caller copies it to the device, 16-byte aligned,
+ * like every other buffer the device calls take. An endpoint's number is its
+ * position in `ids`. m == 0 gives the empty table (16 empty slots). No device
+ * needed.
+ *
+ * YU_EINVAL ([data], Preconditions above), before a byte of h_table is written:
+ * ids or h_table NULL with m > 0; table_bytes != yu_demux_table_bytes(m); m >
+ * YU_DEMUX_MAX_ENDPOINTS; an id that is malformed (proto not 6 or 17, kind > 2,
+ * a field its kind empties not zero, reserved != 0) or that equals an earlier
+ * one (the reference's ErrPortInUse, stack/transport_demuxer.go:69). *bad, where
+ * bad != NULL, receives the index of the first such id, or m when the fault is
+ * not an id; on YU_OK it receives m. YU_ENOMEM: no host memory for the working
+ * copy (as large as the table). */
+int yu_demux_table_fill(const yu_endpoint_id *ids, uint64_t m,
+                        void *h_table, uint64_t table_bytes, uint64_t *bad);
+
+/* Call discipline: that of the other device calls. Every pointer is a DEVICE
+ * pointer; asynchronous on `stream`, no allocation, no synchronisation,
+ * graph-capturable, YU_ENODEV without a device, n == 0 a no-op returning YU_OK
+ * after the checks that do not need n.
+ *
+ * Input: `recs`, n records, 8-byte aligned; `flags`, NULL or n uint16, the `out`
+ * of yu_rx_parse_ragged or yu_rx_split_ragged for these records; `table`, 16-byte
+ * aligned, the bytes yu_demux_table_fill wrote for m ids, table_bytes ==
+ * yu_demux_table_bytes(m).
+ *
+ * Packet i is eligible iff recs[i].proto is 6 or 17 and, with flags != NULL,
+ * (flags[i] & (need | YU_RX_SPLIT)) == (need | YU_RX_SPLIT). A packet without
+ * YU_RX_SPLIT has an all-zero record and is ineligible either way. need == 0 is
+ * the reference, which does not drop on checksum outcomes at this point; need ==
+ * YU_RX_IP_OK | YU_RX_L4_OK is a receiver that does. ICMP and every other
+ * protocol are ineligible: DeliverTransportPacket finds no transport protocol
+ * for them and drops (stack/nic.go:126-130).
+ *
+ * The id of an eligible packet is {LocalPort: dport, LocalAddress: dst,
+ * RemotePort: sport, RemoteAddress: src} (stack/nic.go:144; on receive the
+ * record's dst is local). It is looked up as kind 0 with all four fields, as
+ * kind 1 with the remote fields zero, as kind 2 with the local address zero too,
+ * each with the record's protocol.
+ *   ep[i]        the index of the first hit; YU_DEMUX_NONE when all three miss or
+ *                the packet is ineligible. n DEVICE uint32, every one stored.
+ *   ep_count     NULL, or m + 1 DEVICE uint32 counters the call ADDS to (the
+ *                caller zeroes them; accumulating over several batches is the
+ *                caller's choice): ep_count[e] by the number of packets with
+ *                ep[i] == e, ep_count[m] by the number with YU_DEMUX_NONE. Their
+ *                exclusive sum is the CSR of a grouping by endpoint.
+ *
+ * One launch (yu_rx_demux_variant_n names its kernel). Reads: the records'
+ * first 16 bytes and the dword holding proto, flags, and slots of the table.
+ * Nothing but ep and ep_count is written.
+ *
+ * Out of contract (the table's contents are device memory and are not read on
+ * the host): a table with other contents than yu_demux_table_fill's gives
+ * unspecified ep values and counts, never a fault or a hang: every probe
+ * address lies in table[0, table_bytes); a lookup makes at most table_bytes / 16
+ * probes, even if no slot is empty; an index at or above m read from a slot is
+ * taken as YU_DEMUX_NONE, so no counter outside ep_count[0, m] is touched.
+ * Finite is not fast: on a table without an empty slot every miss walks all
+ * table_bytes / 16 slots, three times per packet, one dependent load after the
+ * other (at m = 2^24 up to about 10^8 probes per packet), so such a call can run
+ * for seconds or, on a large batch, far longer. A table yu_demux_table_fill
+ * wrote is at most half full and its chains are short.
+ *
+ * YU_EINVAL (Preconditions above): [data]: recs or table NULL with n > 0,
+ * table_bytes != yu_demux_table_bytes(m), m > YU_DEMUX_MAX_ENDPOINTS (the last two
+ * checked without n); [out]: ep NULL with n > 0; [offsets]: recs not 8-byte
+ * aligned, table not 16-byte aligned (with n > 0); [side-align]: flags not
+ * 2-byte aligned, ep or ep_count not 4-byte aligned (checked without n). */
+int yu_rx_demux(const yu_tx_record *recs, const uint16_t *flags, uint16_t need,
+                uint64_t n, const void *table, uint64_t table_bytes, uint64_t m,
+                uint32_t *ep, uint32_t *ep_count, void *stream);
+
 /* Host-memory field writer: the matching yu_csum_batch_host_* call (TX modes
  * UDP/TCP/IPV4/ICMP/TX_DATAGRAM only), then each result stored big-endian into the
  * packet's checksum field in host memory, as the device writer does
@@ -983,6 +1103,8 @@ const char *yu_tx_build_variant_n(uint64_t n);
 const char *yu_rx_split_variant_n(uint64_t n);
 /* The header pass of yu_rx_parse_ragged ("k_parse"). No device needed. */
 const char *yu_rx_parse_variant_n(uint64_t n);
+/* The kernel of yu_rx_demux ("k_demux"). No device needed. */
+const char *yu_rx_demux_variant_n(uint64_t n);
 
 #ifdef __cplusplus
 }

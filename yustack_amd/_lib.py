@@ -39,6 +39,12 @@ PROTOTYPES = {
     "yu_rx_split_ragged": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     # data, offsets, n, verify, recs, pay_views, out, stream
     "yu_rx_parse_ragged": (_i32, [_vp, _vp, _u64, _i32, _vp, _vp, _vp, _vp]),
+    "yu_demux_table_bytes": (_u64, [_u64]),
+    "yu_demux_hash": (_u32, [_vp]),
+    # ids, m, h_table, table_bytes, bad
+    "yu_demux_table_fill": (_i32, [_vp, _u64, _vp, _u64, _vp]),
+    # recs, flags, need, n, table, table_bytes, m, ep, ep_count, stream
+    "yu_rx_demux": (_i32, [_vp, _vp, _u16, _u64, _vp, _u64, _u64, _vp, _vp, _vp]),
     **_same("yu_csum_batch_host_uniform yu_csum_fill_host_uniform", _i32, _UNIFORM + [_i32]),  # + device
     **_same("yu_csum_batch_host_ragged yu_csum_fill_host_ragged yu_csum_batch_host_iov yu_csum_fill_host_iov", _i32,
             _RAGGED + [_i32]),
@@ -53,7 +59,8 @@ PROTOTYPES = {
     **_same("yu_ragged_variant_n yu_ragged_fill_variant_n", _str, [_i32, _u64]),
     **_same("yu_iov_variant_n yu_iov_datagram_variant_n yu_iov_pack_variant_n yu_iov_pack_datagram_variant_n", _str,
             [_i32, _u64, _i32]),
-    **_same("yu_tx_build_variant_n yu_rx_split_variant_n yu_rx_parse_variant_n", _str, [_u64]),
+    **_same("yu_tx_build_variant_n yu_rx_split_variant_n yu_rx_parse_variant_n yu_rx_demux_variant_n", _str,
+            [_u64]),
     "yu_host_contexts": (_i32, []),
     "yu_host_staging_bytes": (_u64, [_i32, _vp]),
     "yu_host_staging_trim": (_i32, [_i32]),
@@ -83,6 +90,13 @@ class YuTxRecord(ctypes.Structure):
                 ("window", ctypes.c_uint16), ("flags", ctypes.c_uint8), ("doff", ctypes.c_uint8),
                 ("proto", ctypes.c_uint8), ("ttl", ctypes.c_uint8), ("ip_id", ctypes.c_uint16),
                 ("tos", ctypes.c_uint8), ("reserved", ctypes.c_uint8), ("frag", ctypes.c_uint16)]
+
+
+class YuEndpointId(ctypes.Structure):
+    """struct yu_endpoint_id (include/yucsum.h): one registered endpoint id of the demultiplexer's table."""
+    _fields_ = [("local_addr", ctypes.c_uint8 * 4), ("remote_addr", ctypes.c_uint8 * 4),
+                ("local_port", ctypes.c_uint16), ("remote_port", ctypes.c_uint16), ("proto", ctypes.c_uint8),
+                ("kind", ctypes.c_uint8), ("reserved", ctypes.c_uint16)]
 
 
 class YuError(RuntimeError):

@@ -3,7 +3,8 @@
 Thin Python front end over the C ABI's batched entry points
 (``yu_csum_batch_uniform`` / ``yu_csum_batch_ragged`` / ``yu_csum_batch_iov`` /
 ``yu_csum_batch_iov_datagram`` / ``yu_csum_pack_iov`` / ``yu_csum_pack_iov_datagram`` / ``yu_csum_fill_*`` /
-``yu_tx_build_ragged`` / ``yu_rx_split_ragged`` / ``yu_csum_batch_host_uniform``,
+``yu_tx_build_ragged`` / ``yu_rx_split_ragged`` / ``yu_rx_parse_ragged`` / ``yu_rx_demux`` /
+``yu_csum_batch_host_uniform``,
 include/yucsum.h). PyTorch is used only for device
 memory and streams: the arithmetic happens in the hand-written gfx950 kernels of
 ``csrc/yucsum_kernels.hip``. There is no CPU fallback — without a HIP device every
@@ -30,10 +31,13 @@ TX_DATAGRAM    whole outgoing IPv4 datagrams: both fields (IPv4 header and its
 """
 from __future__ import annotations
 
+import ctypes
+
 import numpy as np
 import torch
 
-from ._lib import check, lib
+from ._lib import YU_EINVAL, check, lib
+from .packets import ENDPOINT_ID
 
 RAW, UDP, TCP, IPV4, ICMP, VERIFY_IPV4, VERIFY_TCP, VERIFY_UDP, VERIFY_RX, TX_DATAGRAM = range(10)
 MODES = {"raw": RAW, "udp": UDP, "tcp": TCP, "ipv4": IPV4, "icmp": ICMP,
@@ -670,6 +674,147 @@ def parse_variant(n: int = 1 << 20) -> str:
     """Name of the kernel of :func:`parse_datagrams`'s header pass for a batch of n packets
     (with ``verify=True`` :func:`ragged_variant` ``("verify_rx", n)`` names the launch before it)."""
     return _wave_variant("rx_parse", n)
+
+
+DEMUX_NONE = 0xFFFFFFFF  # YU_DEMUX_NONE: no endpoint, the reference drops the packet
+DEMUX_MAX_ENDPOINTS = 1 << 24
+
+
+def demux_table(ids, device):
+    """The demultiplexer's table of the registered endpoint ids (yu_demux_table_fill):
+    filled on the host and uploaded to ``device``. ``ids`` is an array of
+    :data:`packets.ENDPOINT_ID` (``packets.endpoint_ids``), or its bytes as shape (m, 16)
+    uint8; an endpoint's number is its position in it. Returns ``(table, m)``, what
+    :func:`demux_datagrams` takes. Raises ValueError naming ``bad``, the index of the first
+    refused id: a malformed one (``proto`` not 6 or 17, ``kind`` over 2, a field its kind
+    empties not zero) or one equal to an earlier id (the reference's ErrPortInUse)."""
+    ids = np.ascontiguousarray(ids)
+    if ids.dtype == np.uint8 and ids.ndim == 2 and ids.shape[1] == ENDPOINT_ID.itemsize:
+        ids = ids.view(ENDPOINT_ID).reshape(ids.shape[0])
+    if ids.dtype != ENDPOINT_ID:
+        raise TypeError("ids must be an array of packets.ENDPOINT_ID (or its bytes, shape (m, 16) uint8)")
+    if ids.ndim != 1:
+        raise ValueError("ids must be one-dimensional")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise TypeError("device must be a CUDA (HIP) device")
+    m = int(ids.shape[0])
+    nbytes = int(lib().yu_demux_table_bytes(m))
+    if nbytes == 0:
+        raise ValueError(f"at most {DEMUX_MAX_ENDPOINTS} endpoint ids")
+    host = np.empty(nbytes, dtype=np.uint8)
+    bad = ctypes.c_uint64(m)
+    rc = lib().yu_demux_table_fill(ids.ctypes.data if m else None, m, host.ctypes.data, nbytes, ctypes.byref(bad))
+    if rc == YU_EINVAL:
+        raise ValueError(f"endpoint id {bad.value} is malformed or equals an earlier id (bad = {bad.value})")
+    check(rc, "yu_demux_table_fill")
+    return torch.from_numpy(host).to(device), m
+
+
+def _dev_u32(t, shape, dev, name):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != dev:
+        raise TypeError(f"{name} must be a CUDA tensor on {dev}")
+    if t.dtype not in (torch.uint32, torch.int32) or not t.is_contiguous():
+        raise TypeError(f"{name} must be a contiguous uint32 (or int32) tensor")
+    if tuple(t.shape) != shape:
+        raise ValueError(f"{name} must have shape {shape}")
+    return t
+
+
+def demux_datagrams(records: torch.Tensor, table: torch.Tensor, m: int, *, flags: torch.Tensor | None = None,
+                    need: int = 0, ep: torch.Tensor | None = None, counts: torch.Tensor | None = None,
+                    group: bool = False, stream: torch.cuda.Stream | None = None):
+    """Transport demultiplexing on the device (yu_rx_demux): which registered endpoint
+    gets each received packet. ``records`` (shape (n, 32) uint8) are
+    :func:`parse_datagrams`' or :func:`split_datagrams`'; ``table, m`` are
+    :func:`demux_table`'s. A packet is eligible when its protocol is 6 or 17 and, with
+    ``flags`` (the ``out`` of the call that stored the records), ``flags[i]`` has every
+    bit of ``need | RX_SPLIT``: ``need=0`` is the reference, which does not drop on
+    checksum outcomes here, ``need=RX_IP_OK | RX_L4_OK`` a receiver that does. Its id
+    (local = the record's ``dst`` and ``dport``, remote = ``src`` and ``sport``) is looked
+    up as a connection, then as a listener on the address, then as a listener on the port.
+
+    Returns ``(ep, counts)``: ``ep[i]`` (uint32) is the first hit's endpoint number, or
+    :data:`DEMUX_NONE` when all three miss or the packet is ineligible; ``counts``
+    (m + 1 uint32) has the packets per endpoint and, at ``[m]``, those without one. The
+    call *adds* to a ``counts`` it is given (to accumulate over batches) and zeroes one it
+    allocates.
+
+    ``group=True`` returns ``(ep, counts, order, first)``: ``order`` is the stable sort of
+    the packet numbers by endpoint (packets without one last) and ``first`` (m + 2 int64)
+    the exclusive sum of ``counts``, so ``order[first[e]:first[e+1]]`` are endpoint e's
+    packets in arrival order and ``order[:first[m]]`` every delivered one. It needs counts
+    that were zero before the call. The grouping is torch operations, not part of the C call;
+    with ``stream`` they run on that stream, behind the kernel, and ``order`` and ``first`` are
+    allocated on it: like ``ep``, they are ready when ``stream`` is, so wait for it before
+    using them on another stream.
+
+    Gathering each endpoint's payloads: with ``views`` from :func:`parse_datagrams` over
+    ``data``, ``sel = order[:first[m]]`` and ``k = sel.numel()``, ::
+
+        vl = views[sel, 1]
+        do = torch.zeros(k + 1, dtype=torch.int64, device=dev); do[1:] = vl.cumsum(0)
+        pack_iov([data], torch.zeros_like(vl), views[sel, 0] - data.data_ptr(), vl,
+                 torch.arange(k + 1, device=dev), "raw", dst_offsets=do)
+
+    leaves endpoint e's payloads contiguous and in arrival order from ``dst[do[first[e]]]``
+    on: one packet stays one scatter-gather packet. An endpoint's whole queue must not be
+    made a single scatter-gather packet, those calls stop at 65535 bytes per packet.
+
+    With ``ep`` and ``counts`` given and ``group=False`` the call is capturable in a graph."""
+    _dev_u8(records, "records")
+    dev = records.device
+    if records.dim() != 2 or records.shape[1] != 32:
+        raise ValueError("records must have shape (n, 32)")
+    n = records.shape[0]
+    if records.data_ptr() % 8:
+        raise TypeError("records must be 8-byte aligned")
+    _dev_u8(table, "table")
+    if table.device != dev:
+        raise TypeError(f"table must be on {dev}")
+    m = int(m)
+    if not 0 <= m <= DEMUX_MAX_ENDPOINTS:
+        raise ValueError(f"m must be 0 .. {DEMUX_MAX_ENDPOINTS}")
+    if table.dim() != 1 or table.numel() != int(lib().yu_demux_table_bytes(m)):
+        raise ValueError("table must hold the yu_demux_table_bytes(m) bytes demux_table returned")
+    if table.data_ptr() % 16:
+        raise TypeError("table must be 16-byte aligned")
+    flags = _opt(flags, torch.uint16, n, dev, "flags")
+    need = int(need)
+    if not 0 <= need <= 0xFFFF:
+        raise ValueError("need must be a combination of the RX_ bits")
+    ep = torch.empty(max(n, 1), dtype=torch.uint32, device=dev)[:n] if ep is None else _dev_u32(ep, (n,), dev, "ep")
+    if counts is None:
+        counts = torch.zeros(m + 1, dtype=torch.uint32, device=dev)
+    else:
+        _dev_u32(counts, (m + 1,), dev, "counts")
+    for k, t in enumerate((ep, counts)):
+        if any(_overlaps(t, s) for s in (records, table, flags, ep)[:3 + k] if s is not None and s.numel()):
+            raise ValueError("ep and counts must overlap nothing the call reads, nor each other")
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream(dev))
+        for t in (records, table, ep, counts) + (() if flags is None else (flags,)):
+            t.record_stream(stream)
+    with torch.cuda.device(dev):
+        rc = lib().yu_rx_demux(records.data_ptr() if n else None, _ptr(flags) if n else None, need, n,
+                               table.data_ptr(), table.numel(), m, ep.data_ptr() if n else None, counts.data_ptr(),
+                               _stream(dev, stream))
+    check(rc, "yu_rx_demux")
+    ep.demux_tables = (records, table, flags)  # read asynchronously: keep them alive
+    if not group:
+        return ep, counts
+    # on the stream the kernel runs on, behind it: ep and counts are read where they were written
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+        key = ep.view(torch.int32).to(torch.int64)
+        order = torch.sort(torch.where(key < 0, m, key), stable=True).indices
+        first = torch.zeros(m + 2, dtype=torch.int64, device=dev)
+        first[1:] = torch.cumsum(counts.view(torch.int32).to(torch.int64), 0)
+    return ep, counts, order, first
+
+
+def demux_variant(n: int = 1 << 20) -> str:
+    """Name of the kernel :func:`demux_datagrams` launches for a batch of n packets."""
+    return _wave_variant("rx_demux", n)
 
 
 def split_variant(n: int = 1 << 20) -> str:

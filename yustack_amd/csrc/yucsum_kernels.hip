@@ -96,6 +96,10 @@
 //     yu::plan_parse): one lane per received datagram, k_split's record and
 //     YU_RX_SPLIT from the packet's first 80 bytes and a view onto the payload,
 //     which is neither read nor copied (yucsum_parse.h).
+//   k_demux<FLAGS, COUNT, NT>: yu_rx_demux (planned by yu::plan_demux): one lane
+//     per record those two store, the three table lookups of the transport
+//     demultiplexer, the endpoint's index per packet and one counter add per
+//     distinct endpoint of a wave step (yucsum_demux.h).
 //   All are grid-stride kernels; the grid is sized per CU and over-subscribed
 //   (see blocks_per_cu in yucsum_plan.cpp), except that k_seg narrows it for
 //   small packets (seg_waves).
@@ -109,6 +113,7 @@
 
 #include "yucsum.h"
 #include "yucsum_build.h"
+#include "yucsum_demux.h"
 #include "yucsum_dense.h"
 #include "yucsum_internal.h"
 #include "yucsum_iov.h"
@@ -3575,6 +3580,78 @@ __global__ __launch_bounds__(256) void k_parse(const uint8_t *data, const uint64
 }
 
 // ---------------------------------------------------------------------
+// k_demux<FLAGS, COUNT, NT>: transport demultiplexing (yu_rx_demux;
+// yucsum_demux.h has the arithmetic): which registered endpoint gets each
+// received packet, from the records k_parse or k_split stored. A lane per
+// packet, 64 per wave step. A lane loads its record's first 16 bytes (addresses,
+// ports) and the dword holding proto, and with FLAGS its flags halfword: the
+// record stream, under the NT policy. An eligible lane then runs the three
+// lookups of deliverPacketLocked one after the other, leaving at the first hit;
+// each probe is one 16-byte load of the slot at 16 * (index & (slots - 1)),
+// always a plain load, because the table is what is reused. The probe loop and
+// the lookups diverge per lane; no lane reads another lane's state, and lanes
+// past n load nothing. `slots` and `m` are kernel arguments computed on the host
+// from the caller's m, never read from the table, so whatever the table holds a
+// probe stays inside it, a lookup ends after `slots` probes, and the index a
+// lane ends with is below m or YU_DEMUX_NONE. ep[i] leaves as one dword store
+// per lane, contiguous across the wave.
+// COUNT: the lanes of a step are converged again after the lookups. While lanes
+// remain uncounted, the first one's value is broadcast, the lanes holding it are
+// balloted, and that first lane alone adds their number to the value's counter:
+// one no-return atomic add per distinct endpoint of the step, at most 64, not
+// one per lane.
+// ---------------------------------------------------------------------
+struct DemuxArgs {
+  const uint8_t *recs;    // yu_tx_record, 32 bytes each, 8-byte aligned
+  const uint16_t *flags;  // FLAGS only
+  const uint8_t *table;   // slots x 16 bytes, 16-byte aligned
+  uint32_t *ep;
+  uint32_t *ep_count;     // COUNT only: m + 1 counters
+  uint64_t n;
+  uint32_t slots, m, need;
+};
+
+struct DemuxLd {
+  const uint8_t *table;
+  __device__ __forceinline__ yu::DemuxSlot operator()(uint32_t i) const {
+    const u32x4 v = *(const u32x4 *)(table + (uint64_t)yu::kDemuxSlotBytes * i);
+    return {v.x, v.y, v.z, v.w};
+  }
+};
+
+template <bool FLAGS, bool COUNT, int NT>
+__global__ __launch_bounds__(256) void k_demux(DemuxArgs A) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t wave = grid_wave(0u);
+  const uint64_t nwave = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  DemuxLd ld = {A.table};
+  for (uint64_t p0 = wave * yu::kDemuxPerWave; p0 < A.n; p0 += nwave * yu::kDemuxPerWave) {
+    const uint64_t p = p0 + lane;
+    const bool act = p < A.n;
+    uint32_t e = yu::kDemuxNone;
+    if (act) {
+      const uint64_t r = (uint64_t)(uintptr_t)A.recs + 32u * p;
+      const u32x4_a8 a = parse_ld<u32x4_a8, NT>(r);
+      const uint32_t proto = yu::demux_rec_proto(parse_ld<uint32_t, NT>(r + 24u));
+      uint32_t fl = 0;
+      if (FLAGS) fl = parse_ld<uint16_t, NT>((uint64_t)(uintptr_t)(A.flags + p));
+      if (yu::demux_eligible(proto, FLAGS, fl, A.need)) e = yu::demux_deliver(ld, A.slots, A.m, a.x, a.y, a.z, proto);
+      A.ep[p] = e;
+    }
+    if (COUNT) {
+      uint64_t todo = __ballot((int)act);
+      while (todo) {  // uniform: every lane of the wave runs the same iterations
+        const uint32_t first = (uint32_t)__ffsll((unsigned long long)todo) - 1u;
+        const uint32_t v = (uint32_t)__builtin_amdgcn_readlane((int)e, (int)first);
+        const uint64_t same = __ballot((int)(act && e == v));
+        if (lane == first) atomicAdd(A.ep_count + yu::demux_counter(v, A.m), (uint32_t)__popcll(same));
+        todo &= ~same;  // `first` is in `same`: at most 64 iterations
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------
 // Host side: launch. Which kernel, form, load policy and grid a batch gets is
 // yu::plan's decision (yucsum_plan.cpp); here are the functions it names.
 // ---------------------------------------------------------------------
@@ -3913,6 +3990,43 @@ int rx_parse(const uint8_t *data, const uint64_t *offsets, uint64_t n, int verif
   return hip_status(hipGetLastError());
 }
 
+// yu_demux_table_fill: its checks, then yu::demux_fill (yucsum_demux.h). Host
+// memory only; no HIP call.
+int demux_table_fill(const yu_endpoint_id *ids, uint64_t m, void *h_table, uint64_t table_bytes, uint64_t *bad) {
+  if (bad) *bad = m;
+  if (m > yu::kDemuxMax || table_bytes != yu::demux_table_bytes(m)) return YU_EINVAL;  // EINVAL:data
+  if (m > 0 && (!ids || !h_table)) return YU_EINVAL;                                   // EINVAL:data
+  const uint64_t b = yu::demux_fill(ids, m, h_table);
+  if (b > m) return YU_ENOMEM;
+  if (bad) *bad = b;
+  if (b < m) return YU_EINVAL;  // EINVAL:data
+  return YU_OK;
+}
+
+// yu_rx_demux: its arguments, then k_demux on yu::plan_demux's grid. The slot
+// count the kernel masks with comes from m here, never from the table.
+int rx_demux(const yu_tx_record *recs, const uint16_t *flags, uint16_t need, uint64_t n, const void *table,
+             uint64_t table_bytes, uint64_t m, uint32_t *ep, uint32_t *ep_count, void *stream) {
+  if (!aligned(flags, 2) || !aligned(ep, 4) || !aligned(ep_count, 4)) return YU_EINVAL;  // EINVAL:side-align
+  if (m > yu::kDemuxMax || table_bytes != yu::demux_table_bytes(m)) return YU_EINVAL;    // EINVAL:data
+  if (n == 0) return YU_OK;
+  if (!ep) return YU_EINVAL;                                     // EINVAL:out
+  if (!aligned(recs, 8) || !aligned(table, 16)) return YU_EINVAL;  // EINVAL:offsets
+  if (!recs || !table) return YU_EINVAL;                         // EINVAL:data
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return hip_status(e);
+  const yu::DemuxPlan p = yu::plan_demux(n, cu_count(dev), yu::env_knobs());
+  const DemuxArgs a = {(const uint8_t *)recs, flags, (const uint8_t *)table, ep, ep_count, n,
+                       yu::demux_slots(m), (uint32_t)m, need};
+  void (*const fn[2][2][2])(DemuxArgs) = {
+      {{k_demux<false, false, 0>, k_demux<false, false, 1>}, {k_demux<false, true, 0>, k_demux<false, true, 1>}},
+      {{k_demux<true, false, 0>, k_demux<true, false, 1>}, {k_demux<true, true, 0>, k_demux<true, true, 1>}}};
+  hipLaunchKernelGGL(fn[flags ? 1 : 0][ep_count ? 1 : 0][p.policy], dim3(p.blocks), dim3(256), 0, (hipStream_t)stream,
+                     a);
+  return hip_status(hipGetLastError());
+}
+
 // Completion signal for the host path's direct mode (yucsum_internal.h):
 // stored after the work before it on the stream, with system-scope release,
 // into coherent pinned host memory.
@@ -4061,6 +4175,23 @@ int yu_rx_parse_ragged(const uint8_t *data, const uint64_t *offsets, uint64_t n,
 
 const char *yu_rx_parse_variant_n(uint64_t n) {
   return yu::plan_parse(n, 256, yu::env_knobs()).name;
+}
+
+uint64_t yu_demux_table_bytes(uint64_t m) { return yu::demux_table_bytes(m); }
+
+uint32_t yu_demux_hash(const yu_endpoint_id *id) { return yu::demux_hash(yu::demux_id_key(*id)); }
+
+int yu_demux_table_fill(const yu_endpoint_id *ids, uint64_t m, void *h_table, uint64_t table_bytes, uint64_t *bad) {
+  return demux_table_fill(ids, m, h_table, table_bytes, bad);
+}
+
+int yu_rx_demux(const yu_tx_record *recs, const uint16_t *flags, uint16_t need, uint64_t n, const void *table,
+                uint64_t table_bytes, uint64_t m, uint32_t *ep, uint32_t *ep_count, void *stream) {
+  return rx_demux(recs, flags, need, n, table, table_bytes, m, ep, ep_count, stream);
+}
+
+const char *yu_rx_demux_variant_n(uint64_t n) {
+  return yu::plan_demux(n, 256, yu::env_knobs()).name;
 }
 
 const char *yu_uniform_variant(uint64_t stride, uint32_t len, int mode,

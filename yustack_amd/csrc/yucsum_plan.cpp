@@ -318,15 +318,14 @@ WavePlan plan_wave(WaveFamily family, uint64_t n, int mode, bool fill, int cus, 
   return p;
 }
 
-// k_parse: a lane per packet, so a wave step takes 64 packets and a block 256.
-// The grid is 8 blocks per CU, every wave slot of a SIMD (the kernel is bound by
-// the latency of its scattered header loads, not by arithmetic), and larger
-// batches stride over it; YU_BLOCKS_PER_CU overrides. Plain loads unless YU_NT is
-// 1: a small packet shares its 128-byte line with its neighbours, which other
-// lanes of the same step read (k_hdr's finding for scattered header reads).
-ParsePlan plan_parse(uint64_t n, int cus, const Knobs &k) {
+// The lane-per-packet kernels (k_parse, k_demux): a wave step takes 64 packets
+// and a block 256. The grid is 8 blocks per CU, every wave slot of a SIMD (these
+// kernels are bound by the latency of scattered loads, not by arithmetic), and
+// larger batches stride over it; YU_BLOCKS_PER_CU overrides. Plain loads of the
+// packet stream unless YU_NT is 1.
+static ParsePlan plan_lane_per_packet(const char *name, uint64_t n, int cus, const Knobs &k) {
   ParsePlan p;
-  p.name = "k_parse";
+  p.name = name;
   p.policy = (uint8_t)(k.nt == 1 ? 1 : 0);
   const uint64_t cap = (uint64_t)cus * (k.blocks_per_cu ? k.blocks_per_cu : 8u);
   uint64_t blocks = (n + 255) / 256;
@@ -335,5 +334,14 @@ ParsePlan plan_parse(uint64_t n, int cus, const Knobs &k) {
   p.blocks = (uint32_t)blocks;
   return p;
 }
+
+// k_parse: the scattered loads are the packets' headers. Plain by default because a
+// small packet shares its 128-byte line with its neighbours, which other lanes of
+// the same step read (k_hdr's finding for scattered header reads).
+ParsePlan plan_parse(uint64_t n, int cus, const Knobs &k) { return plan_lane_per_packet("k_parse", n, cus, k); }
+
+// k_demux: the scattered loads are the table probes, always plain (the table is what
+// is reused); the policy is that of the record stream (yucsum_plan.h).
+DemuxPlan plan_demux(uint64_t n, int cus, const Knobs &k) { return plan_lane_per_packet("k_demux", n, cus, k); }
 
 }  // namespace yu

@@ -4,7 +4,8 @@
 // function table from the same list and launches what the plan names. The
 // wave-per-packet calls (scatter-gather, packing, yu_tx_build_ragged,
 // yu_rx_split_ragged) have the same pair beside it: YU_WAVE_KERNELS and
-// plan_wave; yu_rx_parse_ragged's header pass, a lane per packet, has plan_parse.
+// plan_wave; yu_rx_parse_ragged's header pass, a lane per packet, has plan_parse,
+// and yu_rx_demux's kernel, a lane per record, plan_demux (one rule for both).
 // No HIP call is made here,
 // so tests/cpp/plan_table.cpp and tests/cpp/wave_plan.cpp check every decision
 // on a CPU.
@@ -227,6 +228,13 @@ struct ParsePlan {
   const char *name;  // what yu_rx_parse_variant_n returns
 };
 ParsePlan plan_parse(uint64_t n, int cus, const Knobs &k);
+
+// yu_rx_demux's kernel (k_demux, yucsum_demux.h) is the same mapping, a lane per
+// record, and bound by the same thing, the latency of scattered loads (here the
+// table probes), so it takes plan_parse's rule: one function behind both. The
+// policy is that of the record stream; the table is always read with plain loads.
+typedef ParsePlan DemuxPlan;  // name: what yu_rx_demux_variant_n returns
+DemuxPlan plan_demux(uint64_t n, int cus, const Knobs &k);
 
 }  // namespace yu
 #pragma GCC visibility pop

@@ -20,6 +20,10 @@ and the record layout of the device-side sender, ``batch.build_datagrams``:
 which is also what the device-side receiver, ``batch.split_datagrams``, fills in:
 
 * :data:`RX_SPLIT`, :func:`rx_records`   YU_RX_SPLIT and the records as ``TX_RECORD``
+
+and the registered ids of the device-side demultiplexer, ``batch.demux_table``:
+
+* :data:`ENDPOINT_ID`, :func:`endpoint_ids`  struct yu_endpoint_id (include/yucsum.h)
 """
 from __future__ import annotations
 
@@ -156,6 +160,31 @@ def tx_records(n: int, *, src=0, dst=0, sport=0, dport=0, seq=0, ack=0, window=0
                     ("tos", tos), ("frag", frag)):
         recs[name] = np.broadcast_to(np.asarray(a), (n,))
     return recs
+
+
+# struct yu_endpoint_id (include/yucsum.h): one registered TransportEndpointId plus its
+# protocol for batch.demux_table. Ports in host byte order, addresses as wire bytes.
+ENDPOINT_ID = np.dtype([("local_addr", np.uint8, (4,)), ("remote_addr", np.uint8, (4,)), ("local_port", np.uint16),
+                        ("remote_port", np.uint16), ("proto", np.uint8), ("kind", np.uint8), ("reserved", np.uint16)])
+assert ENDPOINT_ID.itemsize == 16
+
+
+def endpoint_ids(m: int, *, local_addr=0, remote_addr=0, local_port=0, remote_port=0, proto=6, kind=0) -> np.ndarray:
+    """m ids of :data:`ENDPOINT_ID`, each field from an array of m values or a scalar
+    broadcast over them (addresses as for :func:`tx_records`). ``kind`` 0 is a connection
+    (all four fields), 1 a listener on an address (``remote_addr`` and ``remote_port``
+    must be zero), 2 a listener on a port (``local_addr`` zero as well); nothing is
+    zeroed here, ``batch.demux_table`` refuses an id whose emptied fields are not zero.
+    An endpoint's number is its position in the array."""
+    ids = np.zeros(m, dtype=ENDPOINT_ID)
+    for name, a in (("local_addr", local_addr), ("remote_addr", remote_addr)):
+        a = np.asarray(a)
+        if a.ndim == 0:
+            a = np.array([(int(a) >> s) & 0xFF for s in (24, 16, 8, 0)], dtype=np.uint8)
+        ids[name] = np.broadcast_to(a, (m, 4))
+    for name, a in (("local_port", local_port), ("remote_port", remote_port), ("proto", proto), ("kind", kind)):
+        ids[name] = np.broadcast_to(np.asarray(a), (m,))
+    return ids
 
 
 # YU_RX_SPLIT (include/yucsum.h): the bit batch.split_datagrams adds to VERIFY_RX's flags
