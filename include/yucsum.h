@@ -75,10 +75,11 @@ extern "C" {
 /*                  refuse every other mode.                             */
 /*  [out]           out == NULL in a yu_csum_batch_* call, in            */
 /*                  yu_rx_split_ragged or in yu_rx_parse_ragged, ep == NULL */
-/*                  in yu_rx_demux, or h_out ==                          */
+/*                  in yu_rx_demux, order == NULL in yu_rx_group, or h_out == */
 /*                  NULL in a yu_csum_batch_host_* call, with n > 0 (the */
 /*                  fill calls take NULL: no result array; an empty     */
-/*                  batch, n == 0, is a no-op returning YU_OK).          */
+/*                  batch, n == 0, is a no-op returning YU_OK);          */
+/*                  yu_rx_group: first == NULL, with any n.              */
 /*  [fill-mode]     a fill call (yu_csum_fill_*) with a mode that has no */
 /*                  field to write: RAW, VERIFY_* (or no mode at all);   */
 /*                  yu_csum_fill_iov and yu_csum_pack_fill_iov: any mode */
@@ -89,7 +90,8 @@ extern "C" {
 /*                  (yu_tx_build_ragged: out; yu_rx_split_ragged: out,   */
 /*                  and pay_len not 4-byte aligned; yu_rx_parse_ragged:  */
 /*                  out; yu_rx_demux: flags not 2-byte aligned, ep or    */
-/*                  ep_count not 4-byte aligned).                        */
+/*                  ep_count not 4-byte aligned; yu_rx_group: ep or      */
+/*                  order not 4-byte aligned).                           */
 /*  [data]          data == NULL with n > 0 (device calls), h_data ==    */
 /*                  NULL while the packets hold bytes (host calls), iov  */
 /*                  == NULL while first_iov names views; views == NULL  */
@@ -102,7 +104,11 @@ extern "C" {
 /*                  n > 0, table_bytes != yu_demux_table_bytes(m) or m > */
 /*                  YU_DEMUX_MAX_ENDPOINTS (yu_rx_demux); the same two,  */
 /*                  ids or h_table == NULL with m > 0, a malformed id or */
-/*                  one equal to an earlier id (yu_demux_table_fill).    */
+/*                  one equal to an earlier id (yu_demux_table_fill);    */
+/*                  yu_rx_group: m > YU_DEMUX_MAX_ENDPOINTS or n >= 2^32, */
+/*                  and with n > 0: ep or work == NULL, work_bytes below */
+/*                  yu_rx_group_workspace_bytes(n, m), or some but not   */
+/*                  all of views, q_views and q_offsets given.           */
 /*  [len-transport] a packet of a mode other than RAW longer than        */
 /*                  YU_MAX_TRANSPORT_LEN (uniform len; every host ragged */
 /*                  or iov packet). Device ragged batches are not read   */
@@ -124,7 +130,9 @@ extern "C" {
 /*                  8-byte aligned; yu_rx_parse_ragged: offsets == NULL  */
 /*                  or not 8-byte aligned, recs or pay_views not 8-byte  */
 /*                  aligned; yu_rx_demux: recs not 8-byte aligned, table */
-/*                  not 16-byte aligned.                                 */
+/*                  not 16-byte aligned; yu_rx_group: first, q_offsets,  */
+/*                  views or q_views not 8-byte aligned, work not        */
+/*                  16-byte aligned.                                     */
 /*  [iov-view]    a view with base == NULL and len > 0.                */
 /*  [fill-align]    yu_csum_fill_uniform: data or stride not a multiple  */
 /*                  of 4. The uniform writers store whole dwords of each */
@@ -958,6 +966,84 @@ int yu_rx_demux(const yu_tx_record *recs, const uint16_t *flags, uint16_t need,
                 uint64_t n, const void *table, uint64_t table_bytes, uint64_t m,
                 uint32_t *ep, uint32_t *ep_count, void *stream);
 
+/* Grouping by endpoint on the device: the step between yu_rx_demux (decide) and
+ * yu_csum_pack_iov (gather). deliverPacketLocked ends in ep.HandlePacket, which
+ * appends the packet to that endpoint's queue in arrival order (rcvList.PushBack
+ * in transport/udp/endpoint.go, segmentQueue.enqueue in transport/tcp/endpoint.go).
+ * For a batch that is the stable grouping of the packet numbers by endpoint plus
+ * the CSR saying where each endpoint's queue starts. All results are exact
+ * integers.
+ *
+ * Call discipline: that of the other device calls. Every pointer is a DEVICE
+ * pointer; asynchronous on `stream`, no allocation, no synchronisation,
+ * graph-capturable, YU_ENODEV without a device. The scratch memory is therefore
+ * the caller's: `work`, 16-byte aligned, work_bytes >=
+ * yu_rx_group_workspace_bytes(n, m). NOT a no-op at n == 0, unlike every other
+ * device call: the call then stores first[0 .. m+1] = 0 and, where q_offsets !=
+ * NULL, q_offsets[0] = 0, so that no caller ever meets an undefined CSR; it
+ * needs neither ep, order nor work for that, and it needs a device.
+ *
+ *   key(i)     ep[i] if ep[i] < m, else m: YU_DEMUX_NONE and every other value at
+ *              or above m are "no endpoint". ep: n DEVICE uint32 (yu_rx_demux's).
+ *   order[j]   j in [0, n): the packet numbers sorted by (key, i), the stable sort
+ *              by key. n DEVICE uint32, every one stored.
+ *   first[e]   e in [0, m+1]: the number of packets with key < e. m + 2 DEVICE
+ *              uint64, 8-byte aligned, every one stored; first[0] = 0, first[m+1]
+ *              = n. order[first[e] .. first[e+1]) is endpoint e's queue in arrival
+ *              order, order[0 .. first[m]) every delivered packet. Derived from ep
+ *              alone; yu_rx_demux's ep_count, which a caller may have accumulated
+ *              over several batches, is not taken.
+ *   views      NULL, or n yu_iovec, 8-byte aligned (yu_rx_parse_ragged's
+ *              pay_views). Then q_views and q_offsets are required, else both
+ *              must be NULL.
+ *   q_views[j] views[order[j]] for j < first[m], {NULL, 0} for j >= first[m]; n
+ *              yu_iovec, 8-byte aligned.
+ *   q_offsets[j]  the sum of q_views[j'].len over j' < j, modulo 2^64; n + 1 DEVICE
+ *              uint64, 8-byte aligned, q_offsets[0] = 0. (q_views, first_iov = 0,
+ *              1, .., n, q_offsets) is exactly the input of yu_csum_pack_iov(...,
+ *              n, YU_MODE_RAW, ..., dst, q_offsets, out, stream) over all n
+ *              packets: dropped packets copy no byte, and endpoint e's payloads
+ *              lie contiguous and in arrival order at dst[q_offsets[first[e]],
+ *              q_offsets[first[e+1]]). The caller sizes dst on the host by an
+ *              upper bound (the batch's offsets[n], say); nothing is read back.
+ *
+ * yu_rx_group_workspace_bytes(n, m) needs no device, is the same for every
+ * device and is monotone in n; 0 when m > YU_DEMUX_MAX_ENDPOINTS or n >= 2^32
+ * (order holds 32-bit packet numbers). With b = bitlen(m), P = max(1,
+ * ceil(b / 8)) passes, D = max(1, ceil(b / P)) digit bits, B = min(ceil(n /
+ * 1024), 8192) and r16(x) = x rounded up to a multiple of 16, it is
+ *   r16(4 * 2^D * B)                                     the pass histogram
+ * + r16(8 * ceil(max(2^D * B, m + 2, n + 1) / 2048))     the scan's tile sums
+ * + (P > 1 ? r16(4 * (m + 1)) + r16(8 * n) : 0)          key counts, (key, number) pairs
+ * + (P > 2 ? r16(8 * n) : 0)                             the second pair buffer.
+ *
+ * Launches: a stable least-significant-digit radix partition, P passes of a
+ * block histogram, a device-wide exclusive scan (three launches, no block waits
+ * for another) and a scatter; then `first` (read off the histogram when P == 1,
+ * else the scan of the key counts) and, with views, the gather of the views and
+ * the scan of their lengths. yu_rx_group_variant_n names the pass count.
+ *
+ * Writes: nothing but order, first, q_views, q_offsets and work[0,
+ * yu_rx_group_workspace_bytes(n, m)). Reads: ep and views, which must not be
+ * written while the call runs. ep holds arbitrary 32-bit values by the
+ * definition of the key, so there is no out-of-contract ep; if ep changes under
+ * the call the results are unspecified, but every scatter index is compared
+ * with n before its store and no kernel waits for another block: never a
+ * fault, a hang or a store outside the outputs. View lengths are summed as they
+ * stand; yu_csum_pack_iov's own contract handles an oversized one.
+ *
+ * YU_EINVAL (Preconditions above): [offsets]: first, q_offsets, views or q_views
+ * not 8-byte aligned, work not 16-byte aligned; [side-align]: ep or order not
+ * 4-byte aligned; [data], checked without n: m > YU_DEMUX_MAX_ENDPOINTS, n >=
+ * 2^32; [out]: first NULL (with any n), order NULL with n > 0; [data], each with
+ * n > 0: ep or work NULL, work_bytes too small, some but not all of views,
+ * q_views and q_offsets given. The alignments are checked without n. */
+uint64_t yu_rx_group_workspace_bytes(uint64_t n, uint64_t m);
+int yu_rx_group(const uint32_t *ep, uint64_t n, uint64_t m,
+                const yu_iovec *views, uint32_t *order, uint64_t *first,
+                yu_iovec *q_views, uint64_t *q_offsets,
+                void *work, uint64_t work_bytes, void *stream);
+
 /* Host-memory field writer: the matching yu_csum_batch_host_* call (TX modes
  * UDP/TCP/IPV4/ICMP/TX_DATAGRAM only), then each result stored big-endian into the
  * packet's checksum field in host memory, as the device writer does
@@ -1105,6 +1191,10 @@ const char *yu_rx_split_variant_n(uint64_t n);
 const char *yu_rx_parse_variant_n(uint64_t n);
 /* The kernel of yu_rx_demux ("k_demux"). No device needed. */
 const char *yu_rx_demux_variant_n(uint64_t n);
+/* The partition of yu_rx_group by its pass count: "k_group<1>" (m <= 255) ..
+ * "k_group<4>" (m == 2^24); "none" where yu_rx_group_workspace_bytes is 0. No
+ * device needed. */
+const char *yu_rx_group_variant_n(uint64_t n, uint64_t m);
 
 #ifdef __cplusplus
 }

@@ -45,6 +45,10 @@ PROTOTYPES = {
     "yu_demux_table_fill": (_i32, [_vp, _u64, _vp, _u64, _vp]),
     # recs, flags, need, n, table, table_bytes, m, ep, ep_count, stream
     "yu_rx_demux": (_i32, [_vp, _vp, _u16, _u64, _vp, _u64, _u64, _vp, _vp, _vp]),
+    "yu_rx_group_workspace_bytes": (_u64, [_u64, _u64]),
+    # ep, n, m, views, order, first, q_views, q_offsets, work, work_bytes, stream
+    "yu_rx_group": (_i32, [_vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "yu_rx_group_variant_n": (_str, [_u64, _u64]),
     **_same("yu_csum_batch_host_uniform yu_csum_fill_host_uniform", _i32, _UNIFORM + [_i32]),  # + device
     **_same("yu_csum_batch_host_ragged yu_csum_fill_host_ragged yu_csum_batch_host_iov yu_csum_fill_host_iov", _i32,
             _RAGGED + [_i32]),

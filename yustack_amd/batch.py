@@ -4,7 +4,7 @@ Thin Python front end over the C ABI's batched entry points
 (``yu_csum_batch_uniform`` / ``yu_csum_batch_ragged`` / ``yu_csum_batch_iov`` /
 ``yu_csum_batch_iov_datagram`` / ``yu_csum_pack_iov`` / ``yu_csum_pack_iov_datagram`` / ``yu_csum_fill_*`` /
 ``yu_tx_build_ragged`` / ``yu_rx_split_ragged`` / ``yu_rx_parse_ragged`` / ``yu_rx_demux`` /
-``yu_csum_batch_host_uniform``,
+``yu_rx_group`` / ``yu_csum_batch_host_uniform``,
 include/yucsum.h). PyTorch is used only for device
 memory and streams: the arithmetic happens in the hand-written gfx950 kernels of
 ``csrc/yucsum_kernels.hip``. There is no CPU fallback — without a HIP device every
@@ -744,7 +744,9 @@ def demux_datagrams(records: torch.Tensor, table: torch.Tensor, m: int, *, flags
     the packet numbers by endpoint (packets without one last) and ``first`` (m + 2 int64)
     the exclusive sum of ``counts``, so ``order[first[e]:first[e+1]]`` are endpoint e's
     packets in arrival order and ``order[:first[m]]`` every delivered one. It needs counts
-    that were zero before the call. The grouping is torch operations, not part of the C call;
+    that were zero before the call. :func:`group_datagrams` is the same grouping as one C-ABI
+    call (yu_rx_group) that allocates nothing, and with ``views`` it also gives the gather below
+    its table without a host read. Here the grouping is torch operations, not part of the C call;
     with ``stream`` they run on that stream, behind the kernel, and ``order`` and ``first`` are
     allocated on it: like ``ep``, they are ready when ``stream`` is, so wait for it before
     using them on another stream.
@@ -815,6 +817,128 @@ def demux_datagrams(records: torch.Tensor, table: torch.Tensor, m: int, *, flags
 def demux_variant(n: int = 1 << 20) -> str:
     """Name of the kernel :func:`demux_datagrams` launches for a batch of n packets."""
     return _wave_variant("rx_demux", n)
+
+
+def group_workspace_bytes(n: int, m: int) -> int:
+    """Bytes of scratch memory :func:`group_datagrams` needs for n packets and m endpoints
+    (yu_rx_group_workspace_bytes): the same on every device and monotone in n; 0 when
+    ``m > DEMUX_MAX_ENDPOINTS`` or ``n >= 2**32``."""
+    return int(lib().yu_rx_group_workspace_bytes(int(n), int(m)))
+
+
+def group_variant(n: int = 1 << 20, m: int = 1) -> str:
+    """Name of the partition :func:`group_datagrams` runs for n packets and m endpoints:
+    ``k_group<P>`` with P passes (one up to m = 255, two up to 65535, four at 2**24)."""
+    return lib().yu_rx_group_variant_n(int(n), int(m)).decode()
+
+
+def _group_buf(t, dtypes, shape, dev, name):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != dev:
+        raise TypeError(f"{name} must be a CUDA tensor on {dev}")
+    if t.dtype not in dtypes or not t.is_contiguous():
+        raise TypeError(f"{name} must be a contiguous tensor of dtype {' or '.join(str(d) for d in dtypes)}")
+    if tuple(t.shape) != shape:
+        raise ValueError(f"{name} must have shape {shape}")
+    return t
+
+
+def group_datagrams(ep: torch.Tensor, m: int, *, views: torch.Tensor | None = None,
+                    order: torch.Tensor | None = None, first: torch.Tensor | None = None,
+                    q_views: torch.Tensor | None = None, q_offsets: torch.Tensor | None = None,
+                    work: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None):
+    """The packets of a batch grouped by endpoint on the device (yu_rx_group): the step
+    between :func:`demux_datagrams` and :func:`pack_iov`. ``ep`` (n uint32 or int32) is
+    :func:`demux_datagrams`'; a value at or above ``m``, :data:`DEMUX_NONE` among them, is
+    "no endpoint" and has the key ``m``.
+
+    Returns ``(order, first)``: ``order`` (n int32) is the stable sort of the packet numbers
+    by key and ``first`` (m + 2 int64) the number of packets with a key below e, so
+    ``order[first[e]:first[e+1]]`` is endpoint e's queue in arrival order and
+    ``order[:first[m]]`` every delivered packet: what ``demux_datagrams(group=True)``
+    computes with torch operations. ``first`` comes from ``ep`` alone. With n = 0 the call
+    still stores ``first`` (all zero) and ``q_offsets[0]``.
+
+    With ``views`` (shape (n, 2) int64, :func:`parse_datagrams`') it returns ``(order, first,
+    q_views, q_offsets)``: ``q_views[j] = views[order[j]]`` for ``j < first[m]`` and
+    ``(0, 0)`` after, and ``q_offsets`` (n + 1 int64) the exclusive sum of ``q_views[:, 1]``.
+    ``yu_csum_pack_iov(q_views, arange(n + 1), n, RAW, ..., dst, q_offsets, ...)`` over all n
+    packets then leaves endpoint e's payloads contiguous and in arrival order at
+    ``dst[q_offsets[first[e]] : q_offsets[first[e+1]]]``; dropped packets copy nothing, and
+    ``dst`` is sized on the host by an upper bound such as the batch's ``offsets[n]``: no
+    value is read back between the calls.
+
+    ``work`` is the scratch memory, at least :func:`group_workspace_bytes` ``(n, m)`` uint8,
+    16-byte aligned. Buffers not given are allocated; with every buffer given the call is
+    capturable in a graph. ``stream`` as in :func:`demux_datagrams`. ``n >= 2**31`` raises
+    ValueError (``order`` is int32, so that it indexes tensors as it is)."""
+    if not isinstance(ep, torch.Tensor) or not ep.is_cuda:
+        raise TypeError("ep must be a CUDA (HIP) tensor")
+    dev = ep.device
+    if ep.dim() != 1:
+        raise ValueError("ep must be one-dimensional")
+    n = ep.numel()
+    _dev_u32(ep, (n,), dev, "ep")
+    if n >= 1 << 31:
+        raise ValueError("at most 2**31 - 1 packets: order holds int32 packet numbers")
+    m = int(m)
+    if not 0 <= m <= DEMUX_MAX_ENDPOINTS:
+        raise ValueError(f"m must be 0 .. {DEMUX_MAX_ENDPOINTS}")
+    with_views = views is not None
+    if not with_views and (q_views is not None or q_offsets is not None):
+        raise ValueError("q_views and q_offsets go with views")
+    if with_views:
+        _group_buf(views, (torch.int64,), (n, 2), dev, "views")
+    need = group_workspace_bytes(n, m)
+    if order is None:
+        order = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    else:
+        _group_buf(order, (torch.int32, torch.uint32), (n,), dev, "order")
+        order = order.view(torch.int32)
+    if first is None:
+        first = torch.empty(m + 2, dtype=torch.int64, device=dev)
+    else:
+        _group_buf(first, (torch.int64, torch.uint64), (m + 2,), dev, "first")
+        first = first.view(torch.int64)
+    if with_views:
+        if q_views is None:
+            q_views = torch.empty((max(n, 1), 2), dtype=torch.int64, device=dev)[:n]
+        else:
+            _group_buf(q_views, (torch.int64,), (n, 2), dev, "q_views")
+        if q_offsets is None:
+            q_offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        else:
+            _group_buf(q_offsets, (torch.int64, torch.uint64), (n + 1,), dev, "q_offsets")
+            q_offsets = q_offsets.view(torch.int64)
+    if work is None:
+        work = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    else:
+        _dev_u8(work, "work")
+        if work.device != dev:
+            raise TypeError(f"work must be on {dev}")
+        if work.dim() != 1 or work.numel() < need:
+            raise ValueError(f"work must hold group_workspace_bytes(n, m) = {need} bytes")
+        if work.data_ptr() % 16:
+            raise TypeError("work must be 16-byte aligned")
+    reads = tuple(t for t in (ep, views) if t is not None and t.numel())
+    writes = tuple(t for t in (order, first, q_views, q_offsets, work) if t is not None and t.numel())
+    for k, t in enumerate(writes):
+        if any(_overlaps(t, s) for s in reads + writes[:k]):
+            raise ValueError("order, first, q_views, q_offsets and work must overlap nothing the call reads, "
+                             "nor each other")
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream(dev))
+        for t in reads + writes:
+            t.record_stream(stream)
+    with torch.cuda.device(dev):
+        rc = lib().yu_rx_group(ep.data_ptr() if n else None, n, m, _ptr(views) if n else None,
+                               order.data_ptr() if n else None, first.data_ptr(),
+                               _ptr(q_views) if n else None, _ptr(q_offsets), work.data_ptr(), work.numel(),
+                               _stream(dev, stream))
+    check(rc, "yu_rx_group")
+    order.group_tables = (ep, views, work)  # read and written asynchronously: keep them alive
+    if with_views:
+        return order, first, q_views, q_offsets
+    return order, first
 
 
 def split_variant(n: int = 1 << 20) -> str:

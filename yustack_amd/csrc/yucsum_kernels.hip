@@ -100,7 +100,11 @@
 //     per record those two store, the three table lookups of the transport
 //     demultiplexer, the endpoint's index per packet and one counter add per
 //     distinct endpoint of a wave step (yucsum_demux.h).
-//   All are grid-stride kernels; the grid is sized per CU and over-subscribed
+//   k_group_*: yu_rx_group (planned by yu::plan_group): the packet numbers
+//     grouped by endpoint as a stable radix partition, a block histogram, a
+//     device-wide scan and a scatter per pass, and the CSR and the grouped view
+//     table after it (yucsum_group.h). A block per tile, not grid-stride.
+//   All others are grid-stride kernels; the grid is sized per CU and over-subscribed
 //   (see blocks_per_cu in yucsum_plan.cpp), except that k_seg narrows it for
 //   small packets (seg_waves).
 #include <hip/hip_runtime.h>
@@ -115,6 +119,7 @@
 #include "yucsum_build.h"
 #include "yucsum_demux.h"
 #include "yucsum_dense.h"
+#include "yucsum_group.h"
 #include "yucsum_internal.h"
 #include "yucsum_iov.h"
 #include "yucsum_iov_pack.h"
@@ -3652,6 +3657,250 @@ __global__ __launch_bounds__(256) void k_demux(DemuxArgs A) {
 }
 
 // ---------------------------------------------------------------------
+// The kernels of yu_rx_group (yucsum_group.h has the arithmetic and the
+// picture): the packet numbers grouped by endpoint, stable, as a
+// least-significant-digit radix partition of (key, packet number), key =
+// min(ep[i], m), and the scans that turn counts into `first` and the grouped
+// view lengths into q_offsets. Planned by yu::plan_group.
+//   k_group_hist<FIRST, COUNT>    one pass's digit counts per block, digit-major.
+//   k_group_scatter<FIRST, LAST>  the pass's stable scatter to the scanned places.
+//   k_group_scan_sums / _mid / _add   the device-wide exclusive scan.
+//   k_group_first                 one pass only: `first` read off the scanned histogram.
+//   k_group_views                 q_views[j] = views[order[j]], its length to q_offsets[j].
+//   k_group_zero                  dwords set to zero (the key counts; n == 0).
+// FIRST: the pass reads ep and the packet number is the position; otherwise it
+// reads the (key, number) pairs the pass before stored. LAST: it stores `order`
+// alone. No kernel waits for another block; every place a packet number or a
+// view is stored at is compared with n first, and a packet number read back from
+// `order` is compared with n before it indexes `views`, so when ep changes under
+// the call (the histogram and the scatter then disagree) the results are wrong
+// and nothing else happens.
+// ---------------------------------------------------------------------
+struct GroupArgs {
+  const uint32_t *ep;   // FIRST
+  const uint32_t *src;  // !FIRST: n keys, then n packet numbers
+  uint32_t *dst;        // !LAST: n keys, then n packet numbers
+  uint32_t *order;      // LAST
+  uint32_t *hist;       // [1 << digit_bits][blocks]
+  uint32_t *count;      // COUNT: m + 1 key counts, zero before the launch
+  uint64_t n;
+  uint32_t m, pass, digit_bits, tile, blocks;
+};
+
+template <bool FIRST>
+__device__ __forceinline__ uint32_t group_ld_key(const GroupArgs &A, uint64_t i) {
+  return FIRST ? yu::group_key(A.ep[i], A.m) : A.src[i];
+}
+
+// The lanes of the step that hold this lane's digit: one ballot per digit bit,
+// among the active lanes. Every lane of the wave calls it.
+__device__ __forceinline__ uint64_t group_match(bool act, uint32_t d) {
+  uint64_t same = __ballot((int)act);
+#pragma unroll
+  for (uint32_t b = 0; b < 8u; ++b) {
+    const bool bit = (d >> b) & 1u;
+    const uint64_t set = __ballot((int)(act && bit));
+    same &= bit ? set : ~set;
+  }
+  return same;
+}
+
+template <bool FIRST, bool COUNT>
+__global__ __launch_bounds__(256) void k_group_hist(GroupArgs A) {
+  __shared__ uint32_t h[yu::kGroupRadixMax];
+  __shared__ uint32_t none;  // COUNT: the block's packets without an endpoint
+  h[threadIdx.x] = 0;
+  if (threadIdx.x == 0) none = 0;
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint64_t begin = yu::group_wave_begin(blockIdx.x, w, A.tile);
+  const uint32_t steps = yu::group_wave_steps(A.tile);
+  for (uint32_t s = 0; s < steps && begin + 64u * s < A.n; ++s) {  // uniform per wave
+    const uint64_t i = begin + 64u * s + lane;
+    const bool act = i < A.n;
+    uint32_t key = 0;
+    if (act) {
+      key = group_ld_key<FIRST>(A, i);
+      atomicAdd(&h[yu::group_digit(key, A.pass, A.digit_bits)], 1u);
+    }
+    if (COUNT) {
+      // the key m, "no endpoint", is the one every batch may pile up on (a port nobody
+      // listens on): it is counted per block, in LDS, and added once at the end, so an
+      // all-miss batch makes one add per block to count[m], not one per wave step.
+      // Every other key: one add per distinct key of the step, as k_demux counts.
+      const uint64_t miss = __ballot((int)(act && key == A.m));
+      if (lane == 0 && miss) atomicAdd(&none, (uint32_t)__popcll(miss));
+      uint64_t todo = __ballot((int)(act && key != A.m));
+      while (todo) {
+        const uint32_t first = (uint32_t)__ffsll((unsigned long long)todo) - 1u;
+        const uint32_t v = (uint32_t)__builtin_amdgcn_readlane((int)key, (int)first);
+        const uint64_t same = __ballot((int)(act && key == v));
+        if (lane == first) atomicAdd(A.count + v, (uint32_t)__popcll(same));  // v <= m: group_key
+        todo &= ~same;
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < (1u << A.digit_bits))
+    A.hist[yu::group_hist_at(threadIdx.x, blockIdx.x, A.blocks)] = h[threadIdx.x];
+  if (COUNT && threadIdx.x == 0 && none) atomicAdd(A.count + A.m, none);
+}
+
+template <bool FIRST, bool LAST>
+__global__ __launch_bounds__(256) void k_group_scatter(GroupArgs A) {
+  __shared__ uint32_t cnt[yu::kGroupWaves][yu::kGroupRadixMax];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  volatile uint32_t *mine = cnt[w];  // this wave's row: LDS accesses of one wave complete in order
+  for (uint32_t k = 0; k < yu::kGroupRadixMax; k += 64u) mine[k + lane] = 0;
+  const uint64_t begin = yu::group_wave_begin(blockIdx.x, w, A.tile);
+  const uint32_t steps = yu::group_wave_steps(A.tile);
+  // walk 1: this wave's count of every digit; the lowest lane of a digit's lanes adds them
+  for (uint32_t s = 0; s < steps && begin + 64u * s < A.n; ++s) {
+    const uint64_t i = begin + 64u * s + lane;
+    const bool act = i < A.n;
+    const uint32_t d = act ? yu::group_digit(group_ld_key<FIRST>(A, i), A.pass, A.digit_bits) : 0u;
+    const uint64_t same = group_match(act, d);
+    if (act && (same & (((uint64_t)1 << lane) - 1u)) == 0) mine[d] = mine[d] + (uint32_t)__popcll(same);
+    __builtin_amdgcn_wave_barrier();
+  }
+  __syncthreads();
+  {  // counts to places: the scanned histogram, plus the earlier waves of this block
+    const uint32_t d = threadIdx.x;
+    uint32_t at = d < (1u << A.digit_bits) ? A.hist[yu::group_hist_at(d, blockIdx.x, A.blocks)] : 0u;
+    for (uint32_t k = 0; k < yu::kGroupWaves; ++k) {
+      const uint32_t c = cnt[k][d];
+      cnt[k][d] = at;
+      at += c;
+    }
+  }
+  __syncthreads();
+  // walk 2: place = the wave's running place of the digit + the lower lanes holding it
+  for (uint32_t s = 0; s < steps && begin + 64u * s < A.n; ++s) {
+    const uint64_t i = begin + 64u * s + lane;
+    const bool act = i < A.n;
+    const uint32_t key = act ? group_ld_key<FIRST>(A, i) : 0u;
+    const uint32_t d = yu::group_digit(key, A.pass, A.digit_bits);
+    const uint64_t same = group_match(act, d);
+    const uint32_t rank = (uint32_t)__popcll(same & (((uint64_t)1 << lane) - 1u));
+    uint32_t pos = 0;
+    if (act) pos = mine[d] + rank;
+    __builtin_amdgcn_wave_barrier();  // every lane has read before the lowest one writes
+    if (act && rank == 0) mine[d] = pos + (uint32_t)__popcll(same);
+    __builtin_amdgcn_wave_barrier();
+    if (act && pos < A.n) {
+      const uint32_t num = FIRST ? (uint32_t)i : A.src[A.n + i];
+      if (LAST) {
+        A.order[pos] = num;
+      } else {
+        A.dst[pos] = key;
+        A.dst[A.n + pos] = num;
+      }
+    }
+  }
+}
+
+// Exclusive prefix of v over the block's 256 threads in thread order, and the
+// block's total: a shuffle scan per wave, the four wave totals through LDS.
+__device__ __forceinline__ uint64_t group_block_scan(uint64_t v, uint64_t *wsum, uint64_t &total) {
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  unsigned long long incl = v;
+  for (uint32_t o = 1; o < 64u; o <<= 1) {
+    const unsigned long long u = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += u;
+  }
+  if (lane == 63u) wsum[w] = incl;
+  __syncthreads();
+  uint64_t before = 0;
+  total = 0;
+  for (uint32_t k = 0; k < yu::kGroupWaves; ++k) {
+    if (k < w) before += wsum[k];
+    total += wsum[k];
+  }
+  return before + incl - v;
+}
+
+template <typename TIn>
+__global__ __launch_bounds__(256) void k_group_scan_sums(const TIn *in, uint64_t n_in, uint64_t *sums) {
+  __shared__ uint64_t wsum[yu::kGroupWaves];
+  const uint64_t base = (uint64_t)blockIdx.x * yu::kGroupScanTile + threadIdx.x * yu::kGroupScanPer;
+  uint64_t v = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < yu::kGroupScanPer; ++k)
+    if (base + k < n_in) v += in[base + k];
+  uint64_t total;
+  group_block_scan(v, wsum, total);
+  if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+// One block: thread t takes the t-th run of the tile sums.
+__global__ __launch_bounds__(256) void k_group_scan_mid(uint64_t *sums, uint64_t tiles) {
+  __shared__ uint64_t wsum[yu::kGroupWaves];
+  const uint64_t run = yu::group_scan_run(tiles);
+  const uint64_t lo = threadIdx.x * run < tiles ? threadIdx.x * run : tiles;
+  const uint64_t hi = lo + run < tiles ? lo + run : tiles;
+  uint64_t v = 0;
+  for (uint64_t i = lo; i < hi; ++i) v += sums[i];
+  uint64_t total;
+  uint64_t acc = group_block_scan(v, wsum, total);
+  for (uint64_t i = lo; i < hi; ++i) {
+    const uint64_t x = sums[i];
+    sums[i] = acc;
+    acc += x;
+  }
+}
+
+// in == out is allowed: a thread loads its elements before the block's barrier and
+// stores the same positions after it.
+template <typename TIn, typename TOut>
+__global__ __launch_bounds__(256) void k_group_scan_add(const TIn *in, uint64_t n_in, TOut *out, uint64_t n_out,
+                                                        const uint64_t *sums) {
+  __shared__ uint64_t wsum[yu::kGroupWaves];
+  const uint64_t base = (uint64_t)blockIdx.x * yu::kGroupScanTile + threadIdx.x * yu::kGroupScanPer;
+  uint64_t x[yu::kGroupScanPer];
+  uint64_t v = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < yu::kGroupScanPer; ++k) {
+    x[k] = base + k < n_in ? (uint64_t)in[base + k] : 0u;
+    v += x[k];
+  }
+  uint64_t total;
+  uint64_t acc = group_block_scan(v, wsum, total) + sums[blockIdx.x];
+#pragma unroll
+  for (uint32_t k = 0; k < yu::kGroupScanPer; ++k) {
+    if (base + k < n_out) out[base + k] = (TOut)acc;
+    acc += x[k];
+  }
+}
+
+// One pass: the digit is the whole key, so block 0's scanned count of digit e is the
+// number of packets with a key below e.
+__global__ __launch_bounds__(256) void k_group_first(const uint32_t *hist, uint32_t blocks, uint64_t n, uint32_t m,
+                                                     uint64_t *first) {
+  for (uint64_t e = (uint64_t)blockIdx.x * 256u + threadIdx.x; e < (uint64_t)m + 2u; e += (uint64_t)gridDim.x * 256u)
+    first[e] = e <= m ? (uint64_t)hist[yu::group_hist_at((uint32_t)e, 0u, blocks)] : n;
+}
+
+__global__ __launch_bounds__(256) void k_group_views(const uint32_t *order, const uint8_t *views,
+                                                     const uint64_t *first, uint64_t n, uint32_t m, uint8_t *q_views,
+                                                     uint64_t *q_offsets) {
+  const uint64_t delivered = first[m];
+  for (uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x; j < n; j += (uint64_t)gridDim.x * 256u) {
+    const uint32_t o = order[j];
+    u32x4_a8 v = {0u, 0u, 0u, 0u};
+    if (j < delivered && o < n) v = *(const u32x4_a8 *)(views + 16u * (uint64_t)o);
+    *(u32x4_a8 *)(q_views + 16u * j) = v;
+    q_offsets[j] = (uint64_t)v.z | (uint64_t)v.w << 32;  // scanned in place afterwards
+  }
+}
+
+__global__ __launch_bounds__(256) void k_group_zero(uint32_t *p, uint64_t dwords, uint32_t *q, uint64_t q_dwords) {
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < dwords; i += (uint64_t)gridDim.x * 256u) p[i] = 0;
+  if (blockIdx.x == 0 && threadIdx.x < q_dwords) q[threadIdx.x] = 0;
+}
+
+// ---------------------------------------------------------------------
 // Host side: launch. Which kernel, form, load policy and grid a batch gets is
 // yu::plan's decision (yucsum_plan.cpp); here are the functions it names.
 // ---------------------------------------------------------------------
@@ -4027,6 +4276,80 @@ int rx_demux(const yu_tx_record *recs, const uint16_t *flags, uint16_t need, uin
   return hip_status(hipGetLastError());
 }
 
+// The device-wide exclusive scan of yu_rx_group: out[i] = the sum of in[0, i) for
+// i < n_out, inputs at and past n_in taken as 0; `sums` holds one uint64 per tile of
+// kGroupScanTile outputs. Three launches, none waiting for another block. in == out
+// is allowed.
+template <typename TIn, typename TOut>
+void group_scan(const TIn *in, uint64_t n_in, TOut *out, uint64_t n_out, uint64_t *sums, hipStream_t stream) {
+  const uint64_t tiles = yu::group_scan_tiles(n_out);
+  hipLaunchKernelGGL(k_group_scan_sums<TIn>, dim3((uint32_t)tiles), dim3(256), 0, stream, in, n_in, sums);
+  hipLaunchKernelGGL(k_group_scan_mid, dim3(1), dim3(256), 0, stream, sums, tiles);
+  hipLaunchKernelGGL((k_group_scan_add<TIn, TOut>), dim3((uint32_t)tiles), dim3(256), 0, stream, in, n_in, out, n_out,
+                     (const uint64_t *)sums);
+}
+
+// yu_rx_group: its arguments, then yu::plan_group's launches in the caller's
+// workspace. The layout of `work` does not depend on the device.
+int rx_group(const uint32_t *ep, uint64_t n, uint64_t m, const yu_iovec *views, uint32_t *order, uint64_t *first,
+             yu_iovec *q_views, uint64_t *q_offsets, void *work, uint64_t work_bytes, void *stream_) {
+  if (!aligned(first, 8) || !aligned(q_offsets, 8) || !aligned(views, 8) || !aligned(q_views, 8) ||
+      !aligned(work, 16))
+    return YU_EINVAL;                                              // EINVAL:offsets
+  if (!aligned(ep, 4) || !aligned(order, 4)) return YU_EINVAL;     // EINVAL:side-align
+  if (m > yu::kGroupMaxEndpoints || n >= (1ull << 32)) return YU_EINVAL;  // EINVAL:data
+  if (!first) return YU_EINVAL;                                    // EINVAL:out
+  hipStream_t stream = (hipStream_t)stream_;
+  int dev = 0;
+  if (n == 0) {  // the empty CSR is stored: no caller meets an undefined one
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return hip_status(e);
+    hipLaunchKernelGGL(k_group_zero, dim3((uint32_t)((2u * (m + 2u) + 255u) / 256u)), dim3(256), 0, stream,
+                       (uint32_t *)first, 2u * (m + 2u), (uint32_t *)q_offsets, (uint64_t)(q_offsets ? 2u : 0u));
+    return hip_status(hipGetLastError());
+  }
+  if (!order) return YU_EINVAL;                                    // EINVAL:out
+  const yu::GroupPlan p0 = yu::plan_group(n, m, 256, yu::Knobs());
+  if (!ep || !work || work_bytes < p0.bytes) return YU_EINVAL;     // EINVAL:data
+  if ((views != nullptr) != (q_views != nullptr) || (views != nullptr) != (q_offsets != nullptr))
+    return YU_EINVAL;                                              // EINVAL:data
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return hip_status(e);
+  const yu::GroupPlan p = yu::plan_group(n, m, cu_count(dev), yu::env_knobs());
+  uint8_t *const w = (uint8_t *)work;
+  uint32_t *const hist = (uint32_t *)(w + p.hist_off);
+  uint64_t *const sums = (uint64_t *)(w + p.sums_off);
+  uint32_t *const count = (uint32_t *)(w + p.count_off);
+  uint32_t *const pair[2] = {(uint32_t *)(w + p.pair_off[0]), (uint32_t *)(w + p.pair_off[1])};
+  if (p.passes > 1)
+    hipLaunchKernelGGL(k_group_zero, dim3((uint32_t)((m + 256u) / 256u)), dim3(256), 0, stream, count, m + 1u,
+                       (uint32_t *)nullptr, (uint64_t)0);
+  for (uint32_t pass = 0; pass < p.passes; ++pass) {
+    const bool head = pass == 0, last = pass + 1 == p.passes;
+    const GroupArgs a = {ep, head ? nullptr : pair[(pass - 1u) & 1u], last ? nullptr : pair[pass & 1u], order, hist,
+                         count, n, (uint32_t)m, pass, p.digit_bits, p.tile, p.blocks};
+    void (*const hfn)(GroupArgs) = !head ? k_group_hist<false, false>
+                                   : p.passes > 1 ? k_group_hist<true, true> : k_group_hist<true, false>;
+    void (*const sfn[2][2])(GroupArgs) = {{k_group_scatter<false, false>, k_group_scatter<false, true>},
+                                          {k_group_scatter<true, false>, k_group_scatter<true, true>}};
+    const uint64_t cells = ((uint64_t)1 << p.digit_bits) * p.blocks;
+    hipLaunchKernelGGL(hfn, dim3(p.blocks), dim3(256), 0, stream, a);
+    group_scan<uint32_t, uint32_t>(hist, cells, hist, cells, sums, stream);
+    hipLaunchKernelGGL(sfn[head ? 1 : 0][last ? 1 : 0], dim3(p.blocks), dim3(256), 0, stream, a);
+  }
+  if (p.passes == 1)
+    hipLaunchKernelGGL(k_group_first, dim3((uint32_t)((m + 2u + 255u) / 256u)), dim3(256), 0, stream,
+                       (const uint32_t *)hist, p.blocks, n, (uint32_t)m, first);
+  else
+    group_scan<uint32_t, uint64_t>(count, m + 1u, first, m + 2u, sums, stream);
+  if (views) {
+    hipLaunchKernelGGL(k_group_views, dim3(p.lane_blocks), dim3(256), 0, stream, (const uint32_t *)order,
+                       (const uint8_t *)views, (const uint64_t *)first, n, (uint32_t)m, (uint8_t *)q_views, q_offsets);
+    group_scan<uint64_t, uint64_t>(q_offsets, n, q_offsets, n + 1u, sums, stream);
+  }
+  return hip_status(hipGetLastError());
+}
+
 // Completion signal for the host path's direct mode (yucsum_internal.h):
 // stored after the work before it on the stream, with system-scope release,
 // into coherent pinned host memory.
@@ -4192,6 +4515,17 @@ int yu_rx_demux(const yu_tx_record *recs, const uint16_t *flags, uint16_t need, 
 
 const char *yu_rx_demux_variant_n(uint64_t n) {
   return yu::plan_demux(n, 256, yu::env_knobs()).name;
+}
+
+uint64_t yu_rx_group_workspace_bytes(uint64_t n, uint64_t m) { return yu::plan_group(n, m, 256, yu::Knobs()).bytes; }
+
+int yu_rx_group(const uint32_t *ep, uint64_t n, uint64_t m, const yu_iovec *views, uint32_t *order, uint64_t *first,
+                yu_iovec *q_views, uint64_t *q_offsets, void *work, uint64_t work_bytes, void *stream) {
+  return rx_group(ep, n, m, views, order, first, q_views, q_offsets, work, work_bytes, stream);
+}
+
+const char *yu_rx_group_variant_n(uint64_t n, uint64_t m) {
+  return yu::plan_group(n, m, 256, yu::env_knobs()).name;
 }
 
 const char *yu_uniform_variant(uint64_t stride, uint32_t len, int mode,

@@ -6,6 +6,7 @@
 
 #include "yucsum_internal.h"
 #include "yucsum_iov.h"
+#include "yucsum_group.h"  // after yucsum_internal.h, like yucsum_iov.h: YU_IOV_FN needs the HIP runtime's macros here
 
 namespace yu {
 
@@ -343,5 +344,42 @@ ParsePlan plan_parse(uint64_t n, int cus, const Knobs &k) { return plan_lane_per
 // k_demux: the scattered loads are the table probes, always plain (the table is what
 // is reused); the policy is that of the record stream (yucsum_plan.h).
 DemuxPlan plan_demux(uint64_t n, int cus, const Knobs &k) { return plan_lane_per_packet("k_demux", n, cus, k); }
+
+// yu_rx_group: the digit and the pass count follow from m alone (keys are 0 .. m),
+// the tile and the pass kernels' grid from n alone (yucsum_group.h), so the
+// workspace layout is the same on every device. Regions in the order hist, sums,
+// count, pair[0], pair[1], each rounded up to 16 bytes. The histogram is allotted
+// group_blocks_cap(n) blocks, not group_blocks(n): the latter drops where the tile
+// grows, and the workspace must not shrink as n grows. The tile sums serve the
+// longest scan of the call: a pass histogram, the m + 2 entries of `first`, or the
+// n + 1 of q_offsets. The lane-per-element kernels (the view gather, `first` from
+// the histogram) take plan_parse's grid rule.
+GroupPlan plan_group(uint64_t n, uint64_t m, int cus, const Knobs &k) {
+  static const char *const names[4] = {"k_group<1>", "k_group<2>", "k_group<3>", "k_group<4>"};
+  GroupPlan p = {};
+  p.name = "none";
+  if (m > kGroupMaxEndpoints || n >= (1ull << 32)) return p;
+  p.passes = group_passes(m);
+  p.digit_bits = group_digit_bits(m);
+  p.name = names[p.passes - 1];
+  p.tile = group_tile(n);
+  p.blocks = group_blocks(n);
+  p.lane_blocks = plan_lane_per_packet(p.name, n > m + 2 ? n : m + 2, cus, k).blocks;
+  const uint64_t hist = ((uint64_t)1 << p.digit_bits) * group_blocks_cap(n);
+  uint64_t longest = hist > m + 2 ? hist : m + 2;
+  if (n + 1 > longest) longest = n + 1;
+  p.hist_bytes = group_align16(4u * hist);
+  p.sums_bytes = group_align16(8u * group_scan_tiles(longest));
+  p.count_bytes = p.passes > 1 ? group_align16(4u * (m + 1)) : 0u;
+  p.pair_bytes[0] = p.passes > 1 ? group_align16(8u * n) : 0u;
+  p.pair_bytes[1] = p.passes > 2 ? group_align16(8u * n) : 0u;
+  p.hist_off = 0;
+  p.sums_off = p.hist_off + p.hist_bytes;
+  p.count_off = p.sums_off + p.sums_bytes;
+  p.pair_off[0] = p.count_off + p.count_bytes;
+  p.pair_off[1] = p.pair_off[0] + p.pair_bytes[0];
+  p.bytes = p.pair_off[1] + p.pair_bytes[1];
+  return p;
+}
 
 }  // namespace yu

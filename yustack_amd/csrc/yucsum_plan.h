@@ -5,7 +5,8 @@
 // wave-per-packet calls (scatter-gather, packing, yu_tx_build_ragged,
 // yu_rx_split_ragged) have the same pair beside it: YU_WAVE_KERNELS and
 // plan_wave; yu_rx_parse_ragged's header pass, a lane per packet, has plan_parse,
-// and yu_rx_demux's kernel, a lane per record, plan_demux (one rule for both).
+// and yu_rx_demux's kernel, a lane per record, plan_demux (one rule for both);
+// yu_rx_group's launches and workspace have plan_group.
 // No HIP call is made here,
 // so tests/cpp/plan_table.cpp and tests/cpp/wave_plan.cpp check every decision
 // on a CPU.
@@ -235,6 +236,28 @@ ParsePlan plan_parse(uint64_t n, int cus, const Knobs &k);
 // policy is that of the record stream; the table is always read with plain loads.
 typedef ParsePlan DemuxPlan;  // name: what yu_rx_demux_variant_n returns
 DemuxPlan plan_demux(uint64_t n, int cus, const Knobs &k);
+
+// yu_rx_group (yucsum_group.h): a stable radix partition of the packet numbers by
+// endpoint, `passes` passes of a block histogram, a device-wide scan and a scatter,
+// then the CSR and, with views, the grouped view table. Everything the launches
+// need to agree on is here: the digit, the tile, the grids and where each region
+// of the caller's workspace lies. Only lane_blocks depends on the CU count and the
+// knobs (YU_BLOCKS_PER_CU), so yu_rx_group_workspace_bytes needs no device.
+struct GroupPlan {
+  uint32_t digit_bits;   // bits per pass digit, 1 .. 8
+  uint32_t passes;       // 1 .. 4; 0 when the plan is refused (bytes == 0)
+  uint32_t tile;         // packets per block of the pass kernels
+  uint32_t blocks;       // blocks of the pass kernels: ceil(n / tile)
+  uint32_t lane_blocks;  // grid of the lane-per-element kernels (grid-stride)
+  // byte offsets into `work`, each 16-byte aligned; a region of 0 bytes is unused
+  uint64_t hist_off, hist_bytes;        // pass histogram: uint32 [radix][blocks]
+  uint64_t sums_off, sums_bytes;        // the scan's tile sums: uint64
+  uint64_t count_off, count_bytes;      // passes > 1: m + 1 uint32 key counts
+  uint64_t pair_off[2], pair_bytes[2];  // passes > 1 / > 2: n keys then n packet numbers, uint32
+  uint64_t bytes;                       // yu_rx_group_workspace_bytes(n, m)
+  const char *name;                     // what yu_rx_group_variant_n returns
+};
+GroupPlan plan_group(uint64_t n, uint64_t m, int cus, const Knobs &k);
 
 }  // namespace yu
 #pragma GCC visibility pop
