@@ -1044,6 +1044,129 @@ int yu_rx_group(const uint32_t *ep, uint64_t n, uint64_t m,
                 yu_iovec *q_views, uint64_t *q_offsets,
                 void *work, uint64_t work_bytes, void *stream);
 
+/* Answering received datagrams on the device: the step that joins the receive
+ * half (yu_rx_parse_ragged, yu_rx_demux) to the send half (yu_tx_build_iov
+ * below). It is what the reference's samples do with a packet:
+ * sample/tun_udp_echo is ep.Read followed by ep.Write(v, &fullAddr), which ends in
+ * sendUDP(route, v, e.id.LocalPort, to.Port) with the addresses and ports turned
+ * round (transport/udp/endpoint.go:138-187), and ipv4.handleICMP answers every
+ * Echo with sendICMPv4(r, ICMPv4EchoReply, 0, v) once
+ * vv.TrimFront(ICMPv4MinimumSize) has cut the ICMP header off
+ * (network/ipv4/icmp.go:28-63). yu_rx_reply decides which packets of a batch are
+ * answered, stores the replies' records and says where each reply will lie;
+ * yu_tx_build_iov then builds the replies straight from the payload views. So
+ * parse, demux, reply and build are four asynchronous calls on one stream with
+ * no host read and no payload copy between them, and capture as one graph.
+ *
+ * Not modelled: the reply's source address is the request's destination, the
+ * single-address case of FindRoute with an empty bindAddr (stack/stack.go:162; a
+ * stack with several addresses or a bound endpoint may choose another); the UDP
+ * endpoint's rcvBufSizeMax drop (transport/udp/endpoint.go:204: a full receive
+ * queue drops the datagram before the sample reads it); and the TCP
+ * state machine, so TCP segments get no reply here. Only Type() of an ICMP
+ * message is tested, as icmp.go:57 does: the code is ignored, and no checksum
+ * outcome is tested beyond `need`.
+ *
+ * Call discipline: that of yu_rx_group. Every pointer is a DEVICE pointer;
+ * asynchronous on `stream`, no allocation, no synchronisation, graph-capturable,
+ * YU_ENODEV without a device. The scratch memory is the caller's: `work`, 16-byte
+ * aligned, work_bytes >= yu_rx_reply_workspace_bytes(n), which needs no device, is
+ * monotone in n and is the tile sums of one scan over n + 1 outputs: 8 *
+ * ceil((n + 1) / 2048) rounded up to a multiple of 16. NOT a no-op at n == 0: the
+ * call then stores r_offsets[0] = 0, as yu_rx_group stores its empty CSR; it
+ * needs nothing but r_offsets for that, and it needs a device.
+ *
+ * Input: `recs` (n records, 8-byte aligned), `flags` (NULL or n uint16) and
+ * `views` (n yu_iovec, 8-byte aligned) are what yu_rx_parse_ragged stored; `ep`
+ * (n uint32) is yu_rx_demux's output and m its endpoint count; `ep_echo` is NULL
+ * or m bytes, non-zero meaning "this endpoint echoes" (NULL: every endpoint
+ * does). `what` is a combination of the YU_REPLY_ bits. ep may be NULL without
+ * YU_REPLY_UDP_ECHO.
+ *
+ * Per packet i, with the gate of yu_rx_demux (flags == NULL, or (flags[i] &
+ * (need | YU_RX_SPLIT)) == (need | YU_RX_SPLIT)), L = views[i].len and H
+ * yu_tx_build_ragged's transport header length:
+ *   ICMP echo  what & YU_REPLY_ICMP_ECHO, the gate, recs[i].proto == 1 and
+ *              recs[i].sport >> 8 == 8 (Echo). The reply record: src = recs[i].dst,
+ *              dst = recs[i].src, sport = 0 (EchoReply, code 0), proto = 1, ttl =
+ *              64, every other field 0. The payload is the view, S[4:slen].
+ *   UDP echo   what & YU_REPLY_UDP_ECHO, the gate, recs[i].proto == 17, ep[i] < m
+ *              and (ep_echo == NULL or ep_echo[ep[i]] != 0). The reply record:
+ *              src = recs[i].dst, dst = recs[i].src, sport = recs[i].dport, dport =
+ *              recs[i].sport, proto = 17, ttl = 64, every other field 0. The
+ *              payload is the view, S[8:slen].
+ *   no reply   everything else: TCP, other protocols, the all-zero record of a
+ *              packet without YU_RX_SPLIT, and any L > 65535 - 20 - H.
+ *   r_recs[i]  the reply record, or 32 zero bytes. n records, 8-byte aligned.
+ *   T[i]       20 + H + L, or 0 when there is no reply.
+ *   r_offsets[j]  the sum of T[i] over i < j, for j in [0, n]: n + 1 DEVICE uint64,
+ *              8-byte aligned. The replies form a tight ragged batch in arrival
+ *              order in which an unanswered packet is an empty entry:
+ *              yu_tx_build_iov(views, r_recs, n, dst, r_offsets, out, stream)
+ *              builds it, skipping the empty entries. The caller sizes dst on the
+ *              host by an upper bound: a reply has IHL 5 and carries no byte past
+ *              TotalLength, so T[i] is at most the received datagram's length and
+ *              the batch's offsets[n] always suffices. Nothing is read back.
+ *
+ * Launches: k_reply (yu_rx_reply_variant_n), a lane per packet, which leaves T[i]
+ * in r_offsets[i]; then yu_rx_group's device-wide exclusive scan in place (three
+ * launches, no block waits for another).
+ *
+ * Writes: every r_recs[i] and every r_offsets[j] is stored (nothing needs
+ * pre-clearing); nothing else is written except work[0,
+ * yu_rx_reply_workspace_bytes(n)). Reads: recs, flags, views (the table, never
+ * the payload bytes), ep and ep_echo, which must not be written while the call
+ * runs and must not overlap what it writes. ep holds arbitrary 32-bit values (a
+ * value at or above m is "no endpoint"), so the ep_echo index always lies in the
+ * table: never a fault or a hang.
+ *
+ * YU_EINVAL (Preconditions above): [offsets]: recs, views, r_recs or r_offsets
+ * not 8-byte aligned, work not 16-byte aligned; [side-align]: flags not 2-byte
+ * aligned, ep not 4-byte aligned; [data], checked without n: m >
+ * YU_DEMUX_MAX_ENDPOINTS, `what` with unknown bits; [out]: r_offsets NULL (with
+ * any n), r_recs NULL with n > 0; [data], each with n > 0: recs, views or work
+ * NULL, work_bytes too small, ep NULL with YU_REPLY_UDP_ECHO. The alignments are
+ * checked without n. */
+#define YU_REPLY_ICMP_ECHO 1u
+#define YU_REPLY_UDP_ECHO  2u
+uint64_t yu_rx_reply_workspace_bytes(uint64_t n);
+int yu_rx_reply(const yu_tx_record *recs, const uint16_t *flags, uint16_t need,
+                const yu_iovec *views, const uint32_t *ep, uint64_t m,
+                const uint8_t *ep_echo, uint32_t what, uint64_t n,
+                yu_tx_record *r_recs, uint64_t *r_offsets,
+                void *work, uint64_t work_bytes, void *stream);
+
+/* yu_tx_build_ragged with the payloads where they lie: the payload of packet i
+ * is views[i] instead of payload[pay_offsets[i], pay_offsets[i+1]). Everything
+ * else is yu_tx_build_ragged's, word for word: the call discipline (n == 0 a
+ * no-op), recs, dst, dst_offsets, slack, room, the image, the two fields, `out`,
+ * the store rules and the in-contract rules. Two differences:
+ *
+ * The views. n yu_iovec, 8-byte aligned, DEVICE memory; each at any base
+ * alignment and of any length, {NULL, 0} an empty payload. Views may overlap
+ * each other and several packets may name one view; no view may overlap dst
+ * (not checked). Pointers are trusted, as in the scatter-gather calls: bytes are
+ * read only in the dwords holding a view. A view longer than 65535 - 20 - H is
+ * out of contract under the pack calls' rule: the walk stops at the limit,
+ * unspecified bytes stay inside the packet's own span, its out pair is {0, 0};
+ * never a fault or a hang.
+ *
+ * An empty destination span is a skipped packet. A packet with dst_offsets[i+1]
+ * == dst_offsets[i] is skipped by definition, not out of contract: its view is
+ * not dereferenced, its record is ignored, no byte is written and out[2i],
+ * out[2i+1] = 0, 0. That is what lets yu_rx_reply's r_recs and r_offsets and
+ * yu_rx_parse_ragged's view table be passed as they stand.
+ *
+ * One launch (yu_tx_build_iov_variant_n: "k_build<4,iov>"), on
+ * yu_tx_build_ragged's grid.
+ *
+ * YU_EINVAL (Preconditions above): [data]: views, recs or dst NULL with n > 0;
+ * [offsets]: dst_offsets NULL or not 8-byte aligned, views or recs not 8-byte
+ * aligned; [side-align]: out not 2-byte aligned. */
+int yu_tx_build_iov(const yu_iovec *views, const yu_tx_record *recs, uint64_t n,
+                    uint8_t *dst, const uint64_t *dst_offsets,
+                    uint16_t *out, void *stream);
+
 /* Host-memory field writer: the matching yu_csum_batch_host_* call (TX modes
  * UDP/TCP/IPV4/ICMP/TX_DATAGRAM only), then each result stored big-endian into the
  * packet's checksum field in host memory, as the device writer does
@@ -1195,6 +1318,10 @@ const char *yu_rx_demux_variant_n(uint64_t n);
  * "k_group<4>" (m == 2^24); "none" where yu_rx_group_workspace_bytes is 0. No
  * device needed. */
 const char *yu_rx_group_variant_n(uint64_t n, uint64_t m);
+/* The kernel of yu_rx_reply ("k_reply"). No device needed. */
+const char *yu_rx_reply_variant_n(uint64_t n);
+/* The kernel of yu_tx_build_iov ("k_build<4,iov>"). No device needed. */
+const char *yu_tx_build_iov_variant_n(uint64_t n);
 
 #ifdef __cplusplus
 }

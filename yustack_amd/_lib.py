@@ -49,6 +49,12 @@ PROTOTYPES = {
     # ep, n, m, views, order, first, q_views, q_offsets, work, work_bytes, stream
     "yu_rx_group": (_i32, [_vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "yu_rx_group_variant_n": (_str, [_u64, _u64]),
+    "yu_rx_reply_workspace_bytes": (_u64, [_u64]),
+    # recs, flags, need, views, ep, m, ep_echo, what, n, r_recs, r_offsets, work, work_bytes, stream
+    "yu_rx_reply": (_i32, [_vp, _vp, _u16, _vp, _vp, _u64, _vp, _u32, _u64, _vp, _vp, _vp, _u64, _vp]),
+    # views, recs, n, dst, dst_offsets, out, stream
+    "yu_tx_build_iov": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    **_same("yu_rx_reply_variant_n yu_tx_build_iov_variant_n", _str, [_u64]),
     **_same("yu_csum_batch_host_uniform yu_csum_fill_host_uniform", _i32, _UNIFORM + [_i32]),  # + device
     **_same("yu_csum_batch_host_ragged yu_csum_fill_host_ragged yu_csum_batch_host_iov yu_csum_fill_host_iov", _i32,
             _RAGGED + [_i32]),

@@ -941,6 +941,222 @@ def group_datagrams(ep: torch.Tensor, m: int, *, views: torch.Tensor | None = No
     return order, first
 
 
+REPLY_ICMP_ECHO, REPLY_UDP_ECHO = 1, 2  # YU_REPLY_ICMP_ECHO, YU_REPLY_UDP_ECHO
+
+
+def reply_workspace_bytes(n: int) -> int:
+    """Bytes of scratch memory :func:`reply_datagrams` needs for n packets
+    (yu_rx_reply_workspace_bytes): the same on every device and monotone in n."""
+    return int(lib().yu_rx_reply_workspace_bytes(int(n)))
+
+
+def reply_variant(n: int = 1 << 20) -> str:
+    """Name of the kernel :func:`reply_datagrams` launches for a batch of n packets."""
+    return _wave_variant("rx_reply", n)
+
+
+def build_iov_variant(n: int = 1 << 20) -> str:
+    """Name of the kernel :func:`build_datagrams_iov` launches for a batch of n packets."""
+    return _wave_variant("tx_build_iov", n)
+
+
+def reply_datagrams(records: torch.Tensor, views: torch.Tensor, ep: torch.Tensor | None, m: int, *,
+                    flags: torch.Tensor | None = None, need: int = 0,
+                    what: int = REPLY_ICMP_ECHO | REPLY_UDP_ECHO, ep_echo: torch.Tensor | None = None,
+                    r_records: torch.Tensor | None = None, r_offsets: torch.Tensor | None = None,
+                    work: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None):
+    """Which received packets are answered, and with what (yu_rx_reply): the echo of the
+    reference's samples for a batch. ``records``, ``views`` and ``flags`` are
+    :func:`parse_datagrams`' ``(records, views, out)``, ``ep`` and ``m`` :func:`demux_datagrams`'.
+    A packet passes the gate when ``flags`` is None or ``flags[i]`` has every bit of
+    ``need | RX_SPLIT``. With :data:`REPLY_ICMP_ECHO` in ``what`` a gated ICMP Echo request
+    (type 8, any code) is answered with an Echo reply carrying the same bytes; with
+    :data:`REPLY_UDP_ECHO` a gated UDP datagram whose ``ep[i] < m`` is answered with its
+    payload, addresses and ports turned round, unless ``ep_echo`` (m uint8, non-zero: this
+    endpoint echoes) says its endpoint does not. Everything else, TCP included, and any
+    payload that would not fit a 65535-byte datagram, gets no reply. ``ep`` may be None
+    without :data:`REPLY_UDP_ECHO`.
+
+    Returns ``(r_records, r_offsets)``: ``r_records`` (shape (n, 32) uint8) holds the reply
+    records, 32 zero bytes for an unanswered packet, and ``r_offsets`` (n + 1 int64) the
+    exclusive sum of the replies' lengths, 0 for an unanswered packet, so
+    ``build_datagrams_iov(views, r_records, r_offsets, dst)`` builds the replies as a tight
+    ragged batch in arrival order. ``dst`` of the received batch's size always suffices.
+    With n = 0 the call still stores ``r_offsets[0] = 0``.
+
+    ``work`` is the scratch memory, at least :func:`reply_workspace_bytes` ``(n)`` uint8,
+    16-byte aligned. Buffers not given are allocated; with every buffer given the call is
+    capturable in a graph. ``stream`` as in :func:`demux_datagrams`."""
+    _dev_u8(records, "records")
+    dev = records.device
+    if records.dim() != 2 or records.shape[1] != 32:
+        raise ValueError("records must have shape (n, 32)")
+    n = records.shape[0]
+    if records.data_ptr() % 8:
+        raise TypeError("records must be 8-byte aligned")
+    _group_buf(views, (torch.int64,), (n, 2), dev, "views")
+    what = int(what)
+    if what & ~(REPLY_ICMP_ECHO | REPLY_UDP_ECHO) or what < 0:
+        raise ValueError("what must be a combination of REPLY_ICMP_ECHO and REPLY_UDP_ECHO")
+    if ep is None:
+        if what & REPLY_UDP_ECHO:
+            raise ValueError("REPLY_UDP_ECHO needs ep")
+    else:
+        _dev_u32(ep, (n,), dev, "ep")
+    m = int(m)
+    if not 0 <= m <= DEMUX_MAX_ENDPOINTS:
+        raise ValueError(f"m must be 0 .. {DEMUX_MAX_ENDPOINTS}")
+    flags = _opt(flags, torch.uint16, n, dev, "flags")
+    need = int(need)
+    if not 0 <= need <= 0xFFFF:
+        raise ValueError("need must be a combination of the RX_ bits")
+    if ep_echo is not None:
+        _dev_u8(ep_echo, "ep_echo")
+        if ep_echo.device != dev or ep_echo.dim() != 1 or ep_echo.numel() != m:
+            raise ValueError(f"ep_echo must hold m uint8 values on {dev}")
+    if r_records is None:
+        r_records = torch.empty((max(n, 1), 32), dtype=torch.uint8, device=dev)[:n]
+    else:
+        _group_buf(r_records, (torch.uint8,), (n, 32), dev, "r_records")
+        if r_records.data_ptr() % 8:
+            raise TypeError("r_records must be 8-byte aligned")
+    if r_offsets is None:
+        r_offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    else:
+        _group_buf(r_offsets, (torch.int64, torch.uint64), (n + 1,), dev, "r_offsets")
+        r_offsets = r_offsets.view(torch.int64)
+    bytes_needed = reply_workspace_bytes(n)
+    if work is None:
+        work = torch.empty(max(bytes_needed, 16), dtype=torch.uint8, device=dev)
+    else:
+        _dev_u8(work, "work")
+        if work.device != dev:
+            raise TypeError(f"work must be on {dev}")
+        if work.dim() != 1 or work.numel() < bytes_needed:
+            raise ValueError(f"work must hold reply_workspace_bytes(n) = {bytes_needed} bytes")
+        if work.data_ptr() % 16:
+            raise TypeError("work must be 16-byte aligned")
+    reads = tuple(t for t in (records, views, flags, ep, ep_echo) if t is not None and t.numel())
+    writes = tuple(t for t in (r_records, r_offsets, work) if t.numel())
+    for k, t in enumerate(writes):
+        if any(_overlaps(t, s) for s in reads + writes[:k]):
+            raise ValueError("r_records, r_offsets and work must overlap nothing the call reads, nor each other")
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream(dev))
+        for t in reads + writes:
+            t.record_stream(stream)
+    with torch.cuda.device(dev):
+        rc = lib().yu_rx_reply(records.data_ptr() if n else None, _ptr(flags) if n else None, need,
+                               views.data_ptr() if n else None, _ptr(ep) if n else None, m,
+                               _ptr(ep_echo) if n and m else None, what, n, r_records.data_ptr() if n else None,
+                               r_offsets.data_ptr(), work.data_ptr(), work.numel(), _stream(dev, stream))
+    check(rc, "yu_rx_reply")
+    r_offsets.reply_tables = (records, views, flags, ep, ep_echo, work)  # read asynchronously: keep them alive
+    return r_records, r_offsets
+
+
+def build_datagrams_iov(views: torch.Tensor, records: torch.Tensor, dst_offsets: torch.Tensor,
+                        dst: torch.Tensor | None = None, *, out: torch.Tensor | None = None,
+                        stream: torch.cuda.Stream | None = None):
+    """Outgoing IPv4 datagrams built on the device straight from payload views
+    (yu_tx_build_iov): :func:`build_datagrams` with the payload of packet i at the device
+    address ``views[i, 0]``, ``views[i, 1]`` bytes long (shape (n, 2) int64, the table
+    :func:`parse_datagrams` returns, or any addresses of live device memory), so no payload is
+    gathered first. ``records`` are :func:`build_datagrams`'; datagram i goes to
+    ``dst[dst_offsets[i] : dst_offsets[i+1]]`` (n + 1 int64/uint64). A packet whose span is
+    empty is skipped: its view is not read, its record is ignored and its ``out`` pair is 0,
+    so :func:`reply_datagrams`' ``(r_records, r_offsets)`` are passed as they stand. Views may
+    overlap each other; none may overlap ``dst``. The memory behind the views is the
+    caller's to keep alive until the call has run.
+
+    Returns ``(dst, dst_offsets, out)`` as :func:`build_datagrams`. ``dst=None`` reads
+    ``dst_offsets[-1]`` back to size a new one; with every tensor given nothing is read back
+    and the call is capturable in a graph."""
+    _dev_u8(records, "records")
+    dev = records.device
+    if records.dim() != 2 or records.shape[1] != 32:
+        raise ValueError("records must have shape (n, 32)")
+    n = records.shape[0]
+    _group_buf(views, (torch.int64,), (n, 2), dev, "views")
+    if not isinstance(dst_offsets, torch.Tensor) or dst_offsets.dtype not in (torch.int64, torch.uint64) \
+            or not dst_offsets.is_contiguous():
+        raise TypeError("dst_offsets must be a contiguous int64 or uint64 tensor")
+    do = _dev_index(dst_offsets, "dst_offsets", dev, n + 1)
+    if records.data_ptr() % 8 or do.data_ptr() % 8:
+        raise TypeError("records and dst_offsets must be 8-byte aligned")
+    if dst is None:
+        dst = torch.empty(max(int(do[-1].item()), 1), dtype=torch.uint8, device=dev)
+    else:
+        _dev_u8(dst, "dst")
+        if dst.device != dev:
+            raise TypeError(f"dst must be on {dev}")
+        if _overlaps(dst, records) or _overlaps(dst, views) or _overlaps(dst, do):
+            raise ValueError("dst overlaps records, views or dst_offsets")
+    out = _result(out, 2 * n, dev)
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream(dev))
+        for t in (views, records, do, dst, out):
+            t.record_stream(stream)
+    with torch.cuda.device(dev):
+        rc = lib().yu_tx_build_iov(views.data_ptr() if n else None, records.data_ptr() if n else None, n,
+                                   dst.data_ptr(), do.data_ptr(), out.data_ptr() if n else None,
+                                   _stream(dev, stream))
+    check(rc, "yu_tx_build_iov")
+    out.build_tables = (views, records, do)  # the kernel reads them asynchronously: keep them alive with the result
+    return dst, dst_offsets, out
+
+
+def echo_datagrams(data: torch.Tensor, offsets: torch.Tensor, table: torch.Tensor, m: int, *, need: int = 0,
+                   icmp: bool = True, ep_echo: torch.Tensor | None = None, dst: torch.Tensor | None = None,
+                   stream: torch.cuda.Stream | None = None):
+    """A batch of received IPv4 datagrams answered on the device: :func:`parse_datagrams`
+    (with ``verify = need != 0``), yu_rx_demux against ``table, m`` (:func:`demux_table`'s),
+    :func:`reply_datagrams` and :func:`build_datagrams_iov`, four asynchronous calls on one
+    stream with no host read and no payload copy between them. Every UDP datagram that
+    reaches a registered endpoint (one ``ep_echo`` does not switch off) is echoed to its
+    sender, and with ``icmp`` every ICMP Echo request is answered; ``need`` is the gate
+    (``0``: the reference, which does not drop on checksum outcomes; ``RX_IP_OK | RX_L4_OK``:
+    a receiver that does).
+
+    Returns ``(dst, r_offsets, out, flags, ep)``: reply i is ``dst[r_offsets[i] :
+    r_offsets[i+1]]``, empty for a packet that got none, ``out`` its two checksum values,
+    ``flags`` and ``ep`` the parse's and the demultiplexer's results. ``dst`` defaults to
+    ``data.numel()`` bytes, which always suffices: a reply has IHL 5 and carries no byte past
+    TotalLength, so it is never longer than the datagram it answers."""
+    _dev_u8(data, "data")
+    dev = data.device
+    if dst is None:
+        dst = torch.empty(max(data.numel(), 1), dtype=torch.uint8, device=dev)
+    elif _overlaps(_dev_u8(dst, "dst"), data):
+        raise ValueError("dst overlaps data")
+    need = int(need)
+    records, views, flags = parse_datagrams(data, offsets, verify=need != 0, stream=stream)
+    n = records.shape[0]
+    # the demultiplexer without its counters (demux_datagrams always counts)
+    _dev_u8(table, "table")
+    m = int(m)
+    if not 0 <= m <= DEMUX_MAX_ENDPOINTS:
+        raise ValueError(f"m must be 0 .. {DEMUX_MAX_ENDPOINTS}")
+    if table.device != dev or table.dim() != 1 or table.numel() != int(lib().yu_demux_table_bytes(m)) \
+            or table.data_ptr() % 16:
+        raise ValueError("table must be the 16-byte aligned tensor demux_table returned for m ids")
+    ep = torch.empty(max(n, 1), dtype=torch.uint32, device=dev)[:n]
+    if stream is not None:
+        table.record_stream(stream)
+        ep.record_stream(stream)
+    with torch.cuda.device(dev):
+        rc = lib().yu_rx_demux(records.data_ptr() if n else None, flags.data_ptr() if n else None, need, n,
+                               table.data_ptr(), table.numel(), m, ep.data_ptr() if n else None, None,
+                               _stream(dev, stream))
+    check(rc, "yu_rx_demux")
+    what = REPLY_UDP_ECHO | (REPLY_ICMP_ECHO if icmp else 0)
+    r_records, r_offsets = reply_datagrams(records, views, ep, m, flags=flags, need=need, what=what,
+                                           ep_echo=ep_echo, stream=stream)
+    dst, _, out = build_datagrams_iov(views, r_records, r_offsets, dst, stream=stream)
+    out.echo_tables = (data, table, records, r_records, r_offsets)  # the views point into data: keep it alive
+    return dst, r_offsets, out, flags, ep
+
+
 def split_variant(n: int = 1 << 20) -> str:
     """Name of the kernel :func:`split_datagrams` launches for a batch of n packets."""
     return _wave_variant("rx_split", n)

@@ -163,6 +163,12 @@ YU_IOV_FN bool build_in_contract(const BuildRec &R, bool ranged, bool over, uint
   return ranged && !over && T <= kIovLimit && T <= room && tcp_ok;
 }
 
+// yu_tx_build_iov: a packet whose destination span is empty is skipped by
+// definition (its view is not walked, its record is ignored, nothing is stored,
+// its out pair is {0, 0}), so a table with empty entries, as yu_rx_reply leaves
+// for the packets it does not answer, is passed as it stands.
+YU_IOV_FN bool build_iov_skipped(uint64_t o0, uint64_t o1) { return o1 == o0; }
+
 }  // namespace yu
 #pragma GCC visibility pop
 

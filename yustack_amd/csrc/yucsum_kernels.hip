@@ -104,6 +104,12 @@
 //     grouped by endpoint as a stable radix partition, a block histogram, a
 //     device-wide scan and a scatter per pass, and the CSR and the grouped view
 //     table after it (yucsum_group.h). A block per tile, not grid-stride.
+//   k_reply<FLAGS, NT>: yu_rx_reply (planned by yu::plan_reply): one lane per
+//     received packet, the echo's record and length from the packet's record,
+//     view, flags and endpoint; k_group_scan_* then turn the lengths into the
+//     replies' offsets (yucsum_reply.h).
+//   k_build_iov<U, NT>: yu_tx_build_iov (k_build's plan row): k_build with each
+//     payload behind a view, an empty destination span a skipped packet.
 //   All others are grid-stride kernels; the grid is sized per CU and over-subscribed
 //   (see blocks_per_cu in yucsum_plan.cpp), except that k_seg narrows it for
 //   small packets (seg_waves).
@@ -125,6 +131,7 @@
 #include "yucsum_iov_pack.h"
 #include "yucsum_parse.h"
 #include "yucsum_plan.h"
+#include "yucsum_reply.h"
 #include "yucsum_split.h"
 
 namespace {
@@ -3367,6 +3374,94 @@ __global__ __launch_bounds__(256) void k_build(const uint8_t *payload, const uin
 }
 
 // ---------------------------------------------------------------------
+// k_build_iov<U, NT> ("k_build<4,iov>"): k_build with the payload of packet i
+// behind views[i] instead of payload[pay_offsets[i], pay_offsets[i + 1])
+// (yu_tx_build_iov), so that datagrams are built straight from where their
+// payloads lie, inside a received batch for instance. The view is one 16-byte
+// wave-uniform load through the constant address space, issued a packet ahead
+// like the record and the dst_offsets pair; it gives (addr, plen) as they
+// stand, there is no batch end to cut it to. A packet whose destination span is
+// empty is skipped (build_iov_skipped): a wave-uniform branch past the walk and
+// the header, the view's base never used, the out pair {0, 0}. Everything after
+// (addr, plen) is k_build's: range_walk, the header encode, the store rules.
+// It is a kernel of its own, not a third template argument of k_build, so that
+// k_build<4>'s code stays byte for byte what it was; it takes k_build's plan
+// row (grid and load policy) and is no row of YU_WAVE_KERNELS.
+// ---------------------------------------------------------------------
+struct BuildIovPkt {
+  uint64_t base, len;  // views[q]
+  uint64_t o0, o1;     // dst_offsets[q], dst_offsets[q + 1]
+  yu::BuildRec R;
+};
+
+template <int U, int NT>
+__global__ __launch_bounds__(256) void k_build_iov(const yu_iovec *views_, const yu_tx_record *recs_, BuildArgs A) {
+  static_assert(sizeof(yu_iovec) == 16 && offsetof(yu_iovec, len) == 8, "a view is {base, len}, 16 bytes");
+  const YU_CONST_AS uint64_t *views = const_as((const uint64_t *)views_);
+  const YU_CONST_AS uint64_t *dst_offsets = const_as(A.dst_offsets);
+  const YU_CONST_AS uint32_t *recs = const_as((const uint32_t *)recs_);
+  const uint32_t lane = threadIdx.x & 63u;
+  const bool lead = lane == 63;
+  const uint64_t wave = grid_wave(0u);
+  const uint64_t nwave = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  if (wave >= A.n) return;
+  const uint64_t doN = dst_offsets[A.n];
+
+  // Packet q's control data (past the batch: packet 0's again, never used).
+  auto packet = [&](BuildIovPkt &P, uint64_t q) __attribute__((always_inline)) {
+    const uint64_t i = q < A.n ? q : 0;
+    P.base = views[2 * i];
+    P.len = views[2 * i + 1];
+    P.o0 = dst_offsets[i];
+    P.o1 = dst_offsets[i + 1];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) P.R.w[k] = recs[8 * i + k];
+  };
+
+  const PackStore st;
+  BuildIovPkt cur, nx;
+  packet(cur, wave);
+  for (uint64_t p = wave; p < A.n; p += nwave, cur = nx) {
+    packet(nx, p + nwave);
+    if (yu::build_iov_skipped(cur.o0, cur.o1)) {  // wave-uniform: both come from scalar loads
+      if (lead && A.out) A.out[2 * p] = A.out[2 * p + 1] = 0;
+      continue;
+    }
+    const yu::BuildRec R = cur.R;
+    const uint32_t H = yu::build_l4_len(yu::build_proto(R));
+    const uint64_t plen = cur.len, addr = cur.base;
+    const yu::IovPackDst D = {(uint64_t)(uintptr_t)A.dst + cur.o0, yu::iov_pack_room(cur.o0, cur.o1, doN)};
+    yu::IovWalk W;
+    yu::iov_walk_reset(W);
+    W.off = yu::kBuildIp + H;
+    const int32_t vpk = yu::iov_pack_view(addr, W.off);
+    yu::iov_walk_view(W, addr, plen, false, 0u);  // stops at the limit: W.over
+    const uint32_t L = W.off - (yu::kBuildIp + H);  // the bytes taken: T <= 65535
+
+    const uint2 acc = range_walk<U, NT>(W, vpk, D, st, lane, lead);
+    const uint32_t sA = (uint32_t)__builtin_amdgcn_readlane((int)group_total<64>(acc.x), 63);
+    const uint32_t sB = (uint32_t)__builtin_amdgcn_readlane((int)group_total<64>(acc.y), 63);
+    uint32_t ipsum, xsum;
+    yu::build_values(R, H, L, sA, sB, ipsum, xsum);
+
+    // the header, stored last: lane J's destination dword J
+    {
+      const uint32_t hw = yu::build_hdr_src(R, H, L, ipsum, xsum, lane);
+      const uint32_t hprev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hw, 0x111, 0xf, 0xf, true);  // row_shr:1
+      yu::IovPackPlan P;
+      yu::build_hdr_plan(P, D, H);
+      const uint32_t m = lane < yu::kBuildHdrDwords ? yu::iov_pack_mask(P, lane) : 0u;
+      if (m) yu::iov_pack_store(st, (P.pa & ~3ull) + 4u * lane, yu::build_hdr_dst(hw, hprev, P.delta), m);
+    }
+    if (lead && A.out) {
+      const bool ok = yu::build_in_contract(R, true, W.over != 0u, L, D.room);
+      A.out[2 * p] = (uint16_t)(ok ? ipsum : 0u);
+      A.out[2 * p + 1] = (uint16_t)(ok ? xsum : 0u);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------
 // k_split<U, NT>: received IPv4 datagrams taken apart into a 32-byte record, a
 // payload and VERIFY_RX's flags (yu_rx_split_ragged; yucsum_split.h has the
 // arithmetic). k_build run backwards, on the same grid: one wave per packet.
@@ -3653,6 +3748,64 @@ __global__ __launch_bounds__(256) void k_demux(DemuxArgs A) {
         todo &= ~same;  // `first` is in `same`: at most 64 iterations
       }
     }
+  }
+}
+
+// ---------------------------------------------------------------------
+// k_reply<FLAGS, NT>: which received packets are answered, and with what
+// (yu_rx_reply; yucsum_reply.h has the arithmetic): the echo of
+// sample/tun_udp_echo and of ipv4.handleICMP for a batch, from the records and
+// views k_parse stored and the endpoints k_demux chose. A lane per packet, 64
+// per wave step, like both. A lane loads its record as two 16-byte loads and its
+// view's length (the record and view streams, under the NT policy), with FLAGS
+// its flags halfword, as a UDP candidate its ep dword, and, where that index is
+// below m and a table is given, one byte of ep_echo, always a plain load (the
+// table is what is reused). It stores the reply record as two 16-byte stores,
+// 32 zero bytes for no reply, and T, the reply's length or 0, as a uint64 into
+// r_offsets[i]: the launches after this one scan that array in place. No lane
+// reads another lane's state, lanes past n load and store nothing, and m is a
+// kernel argument, so whatever ep holds the ep_echo index stays inside the
+// table. No LDS, no atomics.
+// ---------------------------------------------------------------------
+struct ReplyArgs {
+  const uint8_t *recs;     // yu_tx_record, 32 bytes each, 8-byte aligned
+  const uint16_t *flags;   // FLAGS only
+  const uint8_t *views;    // yu_iovec, 16 bytes each, 8-byte aligned
+  const uint32_t *ep;      // NULL without YU_REPLY_UDP_ECHO
+  const uint8_t *ep_echo;  // NULL, or m bytes
+  uint8_t *r_recs;
+  uint64_t *r_offsets;
+  uint64_t n;
+  uint32_t m, need, what;
+};
+
+template <bool FLAGS, int NT>
+__global__ __launch_bounds__(256) void k_reply(ReplyArgs A) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t wave = grid_wave(0u);
+  const uint64_t nwave = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  const bool have_echo = A.ep_echo != nullptr;
+  for (uint64_t p0 = wave * yu::kReplyPerWave; p0 < A.n; p0 += nwave * yu::kReplyPerWave) {
+    const uint64_t p = p0 + lane;
+    if (p >= A.n) continue;
+    const uint64_t r = (uint64_t)(uintptr_t)A.recs + 32u * p;
+    const u32x4_a8 a = parse_ld<u32x4_a8, NT>(r), b = parse_ld<u32x4_a8, NT>(r + 16u);
+    const uint64_t L = parse_ld<uint64_t, NT>((uint64_t)(uintptr_t)A.views + 16u * p + 8u);
+    uint32_t fl = 0;
+    if (FLAGS) fl = parse_ld<uint16_t, NT>((uint64_t)(uintptr_t)(A.flags + p));
+    const yu::BuildRec in = {{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}};
+    const uint32_t kind = yu::reply_kind(A.what, yu::reply_gate(FLAGS, fl, A.need), yu::build_proto(in), in.w[2]);
+    uint32_t e = yu::kDemuxNone, echo = 0;
+    if (yu::reply_reads_ep(kind)) e = parse_ld<uint32_t, NT>((uint64_t)(uintptr_t)(A.ep + p));
+    if (yu::reply_reads_echo(kind, have_echo, e, A.m)) echo = A.ep_echo[e];
+    yu::BuildRec out;
+    const uint64_t T = yu::reply_make(out, in, L, kind, have_echo, e, A.m, echo);
+    u32x4_a8 r0, r1;
+    r0.x = out.w[0], r0.y = out.w[1], r0.z = out.w[2], r0.w = out.w[3];
+    r1.x = out.w[4], r1.y = out.w[5], r1.z = out.w[6], r1.w = out.w[7];
+    *(u32x4_a8 *)(A.r_recs + 32u * p) = r0;
+    *(u32x4_a8 *)(A.r_recs + 32u * p + 16u) = r1;
+    A.r_offsets[p] = T;
   }
 }
 
@@ -4199,6 +4352,27 @@ int tx_build(const uint8_t *payload, const uint64_t *pay_offsets, const yu_tx_re
   return launch_wave(&WaveFns::build, yu::WaveFamily::Build, n, 0, false, stream, payload, pay_offsets, recs, a);
 }
 
+// yu_tx_build_iov: its arguments, then k_build's plan row for the grid and the
+// load policy, and this call's own kernel by that policy.
+constexpr char kBuildIovName[] = "k_build<4,iov>";
+int tx_build_iov(const yu_iovec *views, const yu_tx_record *recs, uint64_t n, uint8_t *dst,
+                 const uint64_t *dst_offsets, uint16_t *out, void *stream) {
+  if (out && !aligned(out, 2)) return YU_EINVAL;  // EINVAL:side-align
+  if (n == 0) return YU_OK;
+  if (!dst_offsets || !aligned(dst_offsets, 8) || !aligned(views, 8) || !aligned(recs, 8))
+    return YU_EINVAL;  // EINVAL:offsets
+  if (!views || !recs || !dst) return YU_EINVAL;  // EINVAL:data
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return hip_status(e);
+  const yu::WavePlan p = yu::plan_wave(yu::WaveFamily::Build, n, 0, false, cu_count(dev), yu::env_knobs());
+  void (*const fn[3])(const yu_iovec *, const yu_tx_record *, BuildArgs) = {k_build_iov<4, 0>, k_build_iov<4, 1>,
+                                                                            k_build_iov<4, 2>};
+  const BuildArgs a = {dst, dst_offsets, out, n};
+  hipLaunchKernelGGL(fn[p.policy], dim3(p.blocks), dim3(256), 0, (hipStream_t)stream, views, recs, a);
+  return hip_status(hipGetLastError());
+}
+
 // yu_rx_split_ragged: its arguments, then the device's plan and the launch.
 int rx_split(const uint8_t *data, const uint64_t *offsets, uint64_t n, uint8_t *pay, const uint64_t *pay_offsets,
              yu_tx_record *recs, uint32_t *pay_len, uint16_t *out, void *stream) {
@@ -4350,6 +4524,41 @@ int rx_group(const uint32_t *ep, uint64_t n, uint64_t m, const yu_iovec *views, 
   return hip_status(hipGetLastError());
 }
 
+// yu_rx_reply: its arguments, then k_reply on yu::plan_reply's grid, which leaves
+// T[i] in r_offsets[i], and the scan of yu_rx_group over n + 1 outputs in place,
+// its tile sums in the caller's workspace. At n == 0 the one offset is stored.
+int rx_reply(const yu_tx_record *recs, const uint16_t *flags, uint16_t need, const yu_iovec *views,
+             const uint32_t *ep, uint64_t m, const uint8_t *ep_echo, uint32_t what, uint64_t n, yu_tx_record *r_recs,
+             uint64_t *r_offsets, void *work, uint64_t work_bytes, void *stream_) {
+  if (!aligned(recs, 8) || !aligned(views, 8) || !aligned(r_recs, 8) || !aligned(r_offsets, 8) ||
+      !aligned(work, 16))
+    return YU_EINVAL;                                            // EINVAL:offsets
+  if (!aligned(flags, 2) || !aligned(ep, 4)) return YU_EINVAL;   // EINVAL:side-align
+  if (m > yu::kDemuxMax || (what & ~yu::kReplyKnown)) return YU_EINVAL;  // EINVAL:data
+  if (!r_offsets) return YU_EINVAL;                              // EINVAL:out
+  hipStream_t stream = (hipStream_t)stream_;
+  int dev = 0;
+  if (n == 0) {  // the empty batch of replies is stored, as yu_rx_group stores its empty CSR
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return hip_status(e);
+    hipLaunchKernelGGL(k_group_zero, dim3(1), dim3(256), 0, stream, (uint32_t *)r_offsets, (uint64_t)2,
+                       (uint32_t *)nullptr, (uint64_t)0);
+    return hip_status(hipGetLastError());
+  }
+  if (!r_recs) return YU_EINVAL;                                 // EINVAL:out
+  if (!recs || !views || !work || work_bytes < yu::reply_workspace_bytes(n)) return YU_EINVAL;  // EINVAL:data
+  if (!ep && (what & yu::kReplyUdpEcho)) return YU_EINVAL;       // EINVAL:data
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return hip_status(e);
+  const yu::ReplyPlan p = yu::plan_reply(n, cu_count(dev), yu::env_knobs());
+  const ReplyArgs a = {(const uint8_t *)recs, flags, (const uint8_t *)views, ep, ep_echo, (uint8_t *)r_recs,
+                       r_offsets, n, (uint32_t)m, need, what};
+  void (*const fn[2][2])(ReplyArgs) = {{k_reply<false, 0>, k_reply<false, 1>}, {k_reply<true, 0>, k_reply<true, 1>}};
+  hipLaunchKernelGGL(fn[flags ? 1 : 0][p.policy], dim3(p.blocks), dim3(256), 0, stream, a);
+  group_scan<uint64_t, uint64_t>(r_offsets, n, r_offsets, n + 1u, (uint64_t *)work, stream);
+  return hip_status(hipGetLastError());
+}
+
 // Completion signal for the host path's direct mode (yucsum_internal.h):
 // stored after the work before it on the stream, with system-scope release,
 // into coherent pinned host memory.
@@ -4481,6 +4690,13 @@ const char *yu_tx_build_variant_n(uint64_t n) {
   return yu::plan_wave(yu::WaveFamily::Build, n, 0, false, 256, yu::env_knobs()).name;
 }
 
+int yu_tx_build_iov(const yu_iovec *views, const yu_tx_record *recs, uint64_t n, uint8_t *dst,
+                    const uint64_t *dst_offsets, uint16_t *out, void *stream) {
+  return tx_build_iov(views, recs, n, dst, dst_offsets, out, stream);
+}
+
+const char *yu_tx_build_iov_variant_n(uint64_t) { return kBuildIovName; }
+
 int yu_rx_split_ragged(const uint8_t *data, const uint64_t *offsets, uint64_t n, uint8_t *pay,
                        const uint64_t *pay_offsets, yu_tx_record *recs, uint32_t *pay_len, uint16_t *out,
                        void *stream) {
@@ -4526,6 +4742,18 @@ int yu_rx_group(const uint32_t *ep, uint64_t n, uint64_t m, const yu_iovec *view
 
 const char *yu_rx_group_variant_n(uint64_t n, uint64_t m) {
   return yu::plan_group(n, m, 256, yu::env_knobs()).name;
+}
+
+uint64_t yu_rx_reply_workspace_bytes(uint64_t n) { return yu::reply_workspace_bytes(n); }
+
+int yu_rx_reply(const yu_tx_record *recs, const uint16_t *flags, uint16_t need, const yu_iovec *views,
+                const uint32_t *ep, uint64_t m, const uint8_t *ep_echo, uint32_t what, uint64_t n,
+                yu_tx_record *r_recs, uint64_t *r_offsets, void *work, uint64_t work_bytes, void *stream) {
+  return rx_reply(recs, flags, need, views, ep, m, ep_echo, what, n, r_recs, r_offsets, work, work_bytes, stream);
+}
+
+const char *yu_rx_reply_variant_n(uint64_t n) {
+  return yu::plan_reply(n, 256, yu::env_knobs()).name;
 }
 
 const char *yu_uniform_variant(uint64_t stride, uint32_t len, int mode,

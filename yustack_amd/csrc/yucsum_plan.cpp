@@ -345,6 +345,9 @@ ParsePlan plan_parse(uint64_t n, int cus, const Knobs &k) { return plan_lane_per
 // is reused); the policy is that of the record stream (yucsum_plan.h).
 DemuxPlan plan_demux(uint64_t n, int cus, const Knobs &k) { return plan_lane_per_packet("k_demux", n, cus, k); }
 
+// k_reply: every load but the ep_echo byte is a stream read once, lane after lane.
+ReplyPlan plan_reply(uint64_t n, int cus, const Knobs &k) { return plan_lane_per_packet("k_reply", n, cus, k); }
+
 // yu_rx_group: the digit and the pass count follow from m alone (keys are 0 .. m),
 // the tile and the pass kernels' grid from n alone (yucsum_group.h), so the
 // workspace layout is the same on every device. Regions in the order hist, sums,

@@ -5,8 +5,9 @@
 // wave-per-packet calls (scatter-gather, packing, yu_tx_build_ragged,
 // yu_rx_split_ragged) have the same pair beside it: YU_WAVE_KERNELS and
 // plan_wave; yu_rx_parse_ragged's header pass, a lane per packet, has plan_parse,
-// and yu_rx_demux's kernel, a lane per record, plan_demux (one rule for both);
-// yu_rx_group's launches and workspace have plan_group.
+// yu_rx_demux's kernel, a lane per record, plan_demux, and yu_rx_reply's
+// plan_reply (one rule for the three); yu_rx_group's launches and workspace have
+// plan_group. yu_tx_build_iov takes yu_tx_build_ragged's plan_wave row.
 // No HIP call is made here,
 // so tests/cpp/plan_table.cpp and tests/cpp/wave_plan.cpp check every decision
 // on a CPU.
@@ -236,6 +237,14 @@ ParsePlan plan_parse(uint64_t n, int cus, const Knobs &k);
 // policy is that of the record stream; the table is always read with plain loads.
 typedef ParsePlan DemuxPlan;  // name: what yu_rx_demux_variant_n returns
 DemuxPlan plan_demux(uint64_t n, int cus, const Knobs &k);
+
+// yu_rx_reply's kernel (k_reply, yucsum_reply.h) is the same mapping again, a lane
+// per packet over the records, views, flags and endpoints those two calls stored, so
+// it takes the same rule. The policy is that of those streams; the ep_echo table
+// is always read with plain loads. The scan behind it is yu_rx_group's
+// (yucsum_group.h): a block per tile of n + 1 outputs, nothing to plan.
+typedef ParsePlan ReplyPlan;  // name: what yu_rx_reply_variant_n returns
+ReplyPlan plan_reply(uint64_t n, int cus, const Knobs &k);
 
 // yu_rx_group (yucsum_group.h): a stable radix partition of the packet numbers by
 // endpoint, `passes` passes of a block histogram, a device-wide scan and a scatter,
