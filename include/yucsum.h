@@ -109,6 +109,8 @@ extern "C" {
 /*                  and with n > 0: ep or work == NULL, work_bytes below */
 /*                  yu_rx_group_workspace_bytes(n, m), or some but not   */
 /*                  all of views, q_views and q_offsets given.           */
+/*                  yu_rx_stream uses [data], [out], [offsets] and       */
+/*                  [side-align] as the comment above it lists them.     */
 /*  [len-transport] a packet of a mode other than RAW longer than        */
 /*                  YU_MAX_TRANSPORT_LEN (uniform len; every host ragged */
 /*                  or iov packet). Device ragged batches are not read   */
@@ -1167,6 +1169,186 @@ int yu_tx_build_iov(const yu_iovec *views, const yu_tx_record *recs, uint64_t n,
                     uint8_t *dst, const uint64_t *dst_offsets,
                     uint16_t *out, void *stream);
 
+/* TCP segments delivered in order on the device: the step between yu_rx_group
+ * (each endpoint's packets in arrival order) and yu_csum_pack_iov (gather). A UDP
+ * endpoint's queue is its data; a TCP endpoint does not deliver its queue, it runs
+ * receiver.handleRcvdSegment over it (transport/tcp/rcv.go): the acceptability
+ * test against the window, consumeSegment with its trim of bytes already
+ * delivered, the heap of out-of-order segments bounded by pendingBufSize
+ * (segment_heap.go, container/heap), the drain of that heap when a gap closes,
+ * FIN, and an ACK (sendAck -> getSendParams) for everything that is not plain
+ * in-order data. yu_rx_stream is that function for every TCP connection of a
+ * batch at once, with the gates of handleSegments around it (RST, the ACK flag,
+ * the final ACK check). It reads records and view tables only, never a payload
+ * byte. So parse, demux, group, stream and gather, plus yu_tx_build_iov for the
+ * ACKs, are asynchronous calls on one stream with no host read; they capture as
+ * one graph that is replayed batch after batch while the connections' state
+ * lives in device memory.
+ *
+ * Not modelled: the sender half (snd.handleRcvdSegment on the ack field,
+ * retransmission, sendData); maxSegmentsPerWake (a batch is one wake-up); the
+ * segment queue's own limit; one ACK datagram per sendAck (the batch coalesces:
+ * one ACK per connection from the final state, n_acks says how many the
+ * reference would have sent); handshakes and listeners (state 0). The one
+ * departure inside the rule is `cap`, a fixed number of heap entries per endpoint:
+ * a segment that would be parked while pend_count == cap is dropped and ACKed as
+ * if the byte budget were full; cap == 0 is a receiver that keeps nothing out of
+ * order.
+ *
+ * All sequence arithmetic is uint32 and wraps; lt(a, b) is (int32_t)(a - b) < 0
+ * (seqnum.LessThan). Per-connection state, 40 bytes, 8-byte aligned, DEVICE
+ * memory, read and written in place: */
+typedef struct yu_tcp_rcv {
+  uint32_t rcv_nxt, rcv_acc;      /* receiver.rcvNxt, rcvAcc                                 */
+  uint32_t pend_used, pend_size;  /* pendingBufUsed, pendingBufSize                          */
+  uint32_t buf_size, buf_used;    /* endpoint.rcvBufSize, rcvBufUsed (the caller lowers      */
+                                  /* buf_used between calls when the application reads)      */
+  uint32_t snd_nxt;               /* sender.sndNxt: the sequence number an ACK carries       */
+  uint32_t max_sent_ack;          /* sender.maxSentAck                                       */
+  uint32_t pend_count;            /* entries of this endpoint's heap in use                  */
+  uint8_t  wnd_scale;             /* receiver.rcvWndScale                                    */
+  uint8_t  state;                 /* 0 off (not a TCP connection this call serves),          */
+                                  /* 1 open, 2 closed (FIN consumed), 3 reset (RST seen)     */
+  uint16_t reserved;              /* 0 */
+} yu_tcp_rcv;
+
+typedef struct yu_tcp_seg {       /* 32 bytes, one pending segment */
+  yu_iovec data;                  /* its data where it lies, options already cut off         */
+  uint32_t seq;
+  uint32_t pkt;                   /* packet number in the current batch, YU_DEMUX_NONE for   */
+                                  /* a segment carried over from an earlier batch            */
+  uint8_t  flags, reserved[7];
+} yu_tcp_seg;
+
+/* The verdict on one packet, status[i]. */
+#define YU_SEG_NONE          0u  /* no endpoint, a state-0 endpoint, or no usable TCP record */
+#define YU_SEG_CONSUMED      1u  /* in order: delivered (or a pure ACK on rcv_nxt)           */
+#define YU_SEG_CONSUMED_LATE 2u  /* parked in this batch, delivered when the gap closed      */
+#define YU_SEG_PENDING       3u  /* parked in the heap, still there                          */
+#define YU_SEG_DUPLICATE     4u  /* parked in this batch, popped as already acknowledged     */
+#define YU_SEG_DROPPED       5u  /* out of order and no room: byte budget or cap             */
+#define YU_SEG_UNACCEPTABLE  6u  /* outside the window (RFC 793 p. 26): ACKed only           */
+#define YU_SEG_NOOP          7u  /* a pure ACK off rcv_nxt                                   */
+#define YU_SEG_IGNORED       8u  /* no ACK flag                                              */
+#define YU_SEG_AFTER_CLOSE   9u  /* arrived after the FIN was consumed                       */
+#define YU_SEG_RST           10u /* the RST that reset the connection                        */
+#define YU_SEG_UNPROCESSED   11u /* queued behind an RST, or the connection was reset before */
+
+/* Call discipline: that of yu_rx_group. Every pointer is a DEVICE pointer;
+ * asynchronous on `stream`, no allocation, no synchronisation, graph-capturable,
+ * YU_ENODEV without a device. The scratch memory is the caller's: `work`, 16-byte
+ * aligned, work_bytes >= yu_rx_stream_workspace_bytes(n, m, cap), which needs no
+ * device: with N = n + m * cap it is 8 * ceil((max(N, m) + 1) / 2048) rounded up to
+ * a multiple of 16, the tile sums of the longer of the call's two scans; 0 when m >
+ * YU_DEMUX_MAX_ENDPOINTS, n >= 2^32 or cap > 1024. NOT a no-op at n == 0: the empty
+ * tables are stored (every slot {NULL, 0}, every offset 0, every a_recs zero, every
+ * n_acks 0); no state and no heap entry is touched then, and `first` is not read.
+ *
+ * Input: `recs` (n records) and `views` (n yu_iovec) are yu_rx_parse_ragged's
+ * outputs; `order` (n uint32) and `first` (m + 2 uint64) yu_rx_group's; `ids` a
+ * device copy of the m ids yu_demux_table_fill was given (4-byte aligned); `st`, m
+ * yu_tcp_rcv; `heap`, m * cap yu_tcp_seg, 8-byte aligned: endpoint e's heap is
+ * heap[e * cap .. e * cap + st[e].pend_count), container/heap over segmentHeap
+ * with lt on seq as the order (Push appends and sifts up; Pop swaps the first and
+ * last entries, sifts down over the first n - 1 and removes the last), so the
+ * array order is defined exactly and is part of the output.
+ *
+ * The walk for endpoint e goes over its queue order[first[e] .. first[e+1]) in
+ * order; every field below is st[e]'s. An endpoint whose queue is empty is not
+ * touched (the reference only runs on a wake-up); its slots and ACK outputs are
+ * still stored empty. For packet i with record R and view V: opt = R.doff - 20,
+ * dlen = V.len - opt, base = V.base + opt.
+ *   1. state 0: every packet YU_SEG_NONE; st[e] and the heap are not touched.
+ *   2. state 3 at entry: every packet YU_SEG_UNPROCESSED, no ACK, nothing touched.
+ *   3. R.proto != 6, R.doff < 20, opt > V.len or V.len > 65535: YU_SEG_NONE.
+ *   4. R.flags & 4 (RST): YU_SEG_RST, state = 3, every later packet of the queue
+ *      YU_SEG_UNPROCESSED, no final ACK check (handleSegments returns false).
+ *   5. !(R.flags & 16): YU_SEG_IGNORED.
+ *   6. state == 2: YU_SEG_AFTER_CLOSE.
+ *   7. wnd = rcv_acc - rcv_nxt. With wnd == 0 the segment is acceptable iff dlen ==
+ *      0 && seq == rcv_nxt; else iff (seq - rcv_nxt) < wnd, or lt(rcv_nxt, seq +
+ *      dlen) && lt(seq, rcv_acc). Not acceptable: ack(), YU_SEG_UNACCEPTABLE. A
+ *      segment that overshoots rcv_acc is delivered whole; wnd then wraps to a huge
+ *      value, as in the reference.
+ *   8. consume(seq, dlen, base, flags). dlen > 0: fail unless (rcv_nxt - seq) <
+ *      dlen; trim rcv_nxt - seq bytes off the front of seq, dlen and base; append
+ *      {base, dlen} to the endpoint's delivered slots; buf_used += dlen. dlen == 0:
+ *      fail unless seq == rcv_nxt. Then rcv_nxt = seq + dlen; with FIN rcv_nxt++,
+ *      ack(), state = 2.
+ *   9. consume failed: with dlen > 0 or FIN the segment is parked if pend_used <
+ *      pend_size && pend_count < cap (pend_used += dlen + SYN + FIN,
+ *      YU_SEG_PENDING, its heap entry holds {base, dlen}, seq, pkt = i, flags), else
+ *      YU_SEG_DROPPED; ack() either way. A pure ACK off rcv_nxt: YU_SEG_NOOP.
+ *  10. consume succeeded: YU_SEG_CONSUMED, then the drain: while state == 1 and
+ *      pend_count > 0, with t the heap's first entry: if !lt(t.seq + t.len - 1,
+ *      rcv_nxt) and consume(t) fails, stop; else pop t and pend_used -= its
+ *      logical length AFTER consume's trim (the reference subtracts the trimmed
+ *      length, so the budget can stay above zero). A popped entry with pkt !=
+ *      YU_DEMUX_NONE gets YU_SEG_CONSUMED_LATE if consumed, YU_SEG_DUPLICATE if
+ *      skipped as already acknowledged. (A parked FIN without data is popped as
+ *      acknowledged when reached, t.seq - 1 being below rcv_nxt: the reference's
+ *      behaviour.)
+ *  11. end of the queue, state 1 or 2: if rcv_nxt != max_sent_ack, ack(). After a
+ *      walk that touched the state every remaining heap entry gets pkt =
+ *      YU_DEMUX_NONE.
+ * ack(): n_acks++; avail = buf_used >= buf_size ? 0 : buf_size - buf_used; acc =
+ * rcv_nxt + avail; if lt(rcv_acc, acc) rcv_acc = acc; max_sent_ack = rcv_nxt.
+ *
+ * Output, with N = n + m * cap:
+ *   status     n bytes, every one stored; packets without an endpoint
+ *              (order[first[m] .. n)) get YU_SEG_NONE.
+ *   s_views    N yu_iovec, 8-byte aligned, every one stored. Endpoint e owns the
+ *              slots [first[e] + e * cap, first[e+1] + (e + 1) * cap); its delivered
+ *              views fill them from the front in delivery order, the rest and the
+ *              slots from first[m] + m * cap on are {NULL, 0}.
+ *   s_offsets  N + 1 uint64, the exclusive sum of the slot lengths. (s_views,
+ *              first_iov = 0 .. N, s_offsets) is yu_csum_pack_iov(RAW)'s input as it
+ *              stands; connection e's new in-order bytes lie at dst[s_offsets[lo],
+ *              s_offsets[hi]) with [lo, hi) its slots.
+ *   a_recs     m records: per endpoint with n_acks > 0 the ACK from the final state
+ *              (sendTCP's fields): src, dst = ids[e].local_addr, remote_addr; sport,
+ *              dport = local_port, remote_port; seq = snd_nxt; ack = rcv_nxt; window
+ *              = min((rcv_acc - rcv_nxt) >> wnd_scale, 0xFFFF); flags 16, doff 20,
+ *              proto 6, ttl 64, everything else 0. 32 zero bytes otherwise.
+ *   a_offsets  m + 1 uint64: the exclusive sum of 40 per endpoint with an ACK.
+ *              yu_tx_build_iov(zero_views, a_recs, m, dst, a_offsets, ..) builds the
+ *              ACK datagrams from a zeroed m-entry view table the caller supplies.
+ *   n_acks     m uint32, stored, not added to: the ACKs the reference would have sent.
+ * a_recs, a_offsets and n_acks are all NULL or all given.
+ *
+ * Lifetime: a parked segment's view points into the batch it arrived in. The
+ * caller keeps that memory until the segment has been delivered or the connection
+ * is torn down. cap = 0 avoids it.
+ *
+ * Launches: k_stream (yu_rx_stream_variant_n), a wave per endpoint on a
+ * grid-stride loop, 64 queue entries per wave step, a run of plain in-order
+ * segments taken 64 at a time; then yu_rx_group's device-wide exclusive scan in
+ * place over s_offsets and, with the ACK outputs, over a_offsets.
+ *
+ * Out of contract (the tables are device memory and are not read on the host),
+ * with unspecified results for the endpoints concerned only: order values at or
+ * above n, a `first` that is not monotone or exceeds n, pend_count > cap, a heap
+ * that is not heap-ordered. Every index is compared with its bound before use and
+ * every loop is bounded by the queue length or by cap: never a fault, a hang or a
+ * store outside the outputs.
+ *
+ * YU_EINVAL (Preconditions above): [offsets]: recs, views, first, st, heap,
+ * s_views, s_offsets, a_recs or a_offsets not 8-byte aligned, work not 16-byte
+ * aligned; [side-align]: order, ids or n_acks not 4-byte aligned; [data], checked
+ * without n: m > YU_DEMUX_MAX_ENDPOINTS, n >= 2^32, cap > 1024, st NULL with m > 0,
+ * some but not all of a_recs, a_offsets and n_acks given; [out]: s_offsets NULL
+ * with m > 0 (any n) or n > 0, status or s_views NULL with n > 0, s_views NULL
+ * with m * cap > 0; [data], each with n > 0: recs, views, order, first or work
+ * NULL, work_bytes too small, heap NULL with m * cap > 0, ids NULL with the ACK
+ * outputs and m > 0. The alignments are checked without n. */
+uint64_t yu_rx_stream_workspace_bytes(uint64_t n, uint64_t m, uint32_t cap);
+int yu_rx_stream(const yu_tx_record *recs, const yu_iovec *views, uint64_t n,
+                 const uint32_t *order, const uint64_t *first, uint64_t m,
+                 const yu_endpoint_id *ids, yu_tcp_rcv *st, yu_tcp_seg *heap, uint32_t cap,
+                 uint8_t *status, yu_iovec *s_views, uint64_t *s_offsets,
+                 yu_tx_record *a_recs, uint64_t *a_offsets, uint32_t *n_acks,
+                 void *work, uint64_t work_bytes, void *stream);
+
 /* Host-memory field writer: the matching yu_csum_batch_host_* call (TX modes
  * UDP/TCP/IPV4/ICMP/TX_DATAGRAM only), then each result stored big-endian into the
  * packet's checksum field in host memory, as the device writer does
@@ -1320,6 +1502,10 @@ const char *yu_rx_demux_variant_n(uint64_t n);
 const char *yu_rx_group_variant_n(uint64_t n, uint64_t m);
 /* The kernel of yu_rx_reply ("k_reply"). No device needed. */
 const char *yu_rx_reply_variant_n(uint64_t n);
+/* The kernel of yu_rx_stream ("k_stream"; "k_stream<walk>" where the tuning value
+ * YU_STREAM=walk forces the general step for every entry); "none" where
+ * yu_rx_stream_workspace_bytes is 0. No device needed. */
+const char *yu_rx_stream_variant_n(uint64_t n, uint64_t m, uint32_t cap);
 /* The kernel of yu_tx_build_iov ("k_build<4,iov>"). No device needed. */
 const char *yu_tx_build_iov_variant_n(uint64_t n);
 

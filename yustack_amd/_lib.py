@@ -55,6 +55,12 @@ PROTOTYPES = {
     # views, recs, n, dst, dst_offsets, out, stream
     "yu_tx_build_iov": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     **_same("yu_rx_reply_variant_n yu_tx_build_iov_variant_n", _str, [_u64]),
+    "yu_rx_stream_workspace_bytes": (_u64, [_u64, _u64, _u32]),
+    # recs, views, n, order, first, m, ids, st, heap, cap, status, s_views, s_offsets, a_recs, a_offsets, n_acks,
+    # work, work_bytes, stream
+    "yu_rx_stream": (_i32, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                            _u64, _vp]),
+    "yu_rx_stream_variant_n": (_str, [_u64, _u64, _u32]),
     **_same("yu_csum_batch_host_uniform yu_csum_fill_host_uniform", _i32, _UNIFORM + [_i32]),  # + device
     **_same("yu_csum_batch_host_ragged yu_csum_fill_host_ragged yu_csum_batch_host_iov yu_csum_fill_host_iov", _i32,
             _RAGGED + [_i32]),

@@ -1157,6 +1157,250 @@ def echo_datagrams(data: torch.Tensor, offsets: torch.Tensor, table: torch.Tenso
     return dst, r_offsets, out, flags, ep
 
 
+STREAM_MAX_CAP = 1024
+# YU_SEG_*: the verdict on one packet (include/yucsum.h)
+SEG_NONE, SEG_CONSUMED, SEG_CONSUMED_LATE, SEG_PENDING, SEG_DUPLICATE, SEG_DROPPED, SEG_UNACCEPTABLE, SEG_NOOP, \
+    SEG_IGNORED, SEG_AFTER_CLOSE, SEG_RST, SEG_UNPROCESSED = range(12)
+
+
+def stream_workspace_bytes(n: int, m: int, cap: int) -> int:
+    """Bytes of scratch memory :func:`stream_datagrams` needs for n packets, m endpoints and
+    ``cap`` heap entries per endpoint (yu_rx_stream_workspace_bytes); 0 when
+    ``m > DEMUX_MAX_ENDPOINTS``, ``n >= 2**32`` or ``cap > STREAM_MAX_CAP``."""
+    return int(lib().yu_rx_stream_workspace_bytes(int(n), int(m), int(cap)))
+
+
+def stream_variant(n: int = 1 << 20, m: int = 1, cap: int = 0) -> str:
+    """Name of the kernel :func:`stream_datagrams` launches (``k_stream``)."""
+    return lib().yu_rx_stream_variant_n(int(n), int(m), int(cap)).decode()
+
+
+def tcp_receivers(m: int, cap: int, device, state=None):
+    """The per-connection state of :func:`stream_datagrams` on the device: ``(st, heap)``,
+    ``st`` of shape (m, 40) uint8 from the host array ``state`` (m entries of
+    ``packets.TCP_RCV``, e.g. ``packets.tcp_rcv``; None: every endpoint in state 0) and
+    ``heap`` of shape (m * cap, 32) uint8, zeroed. Both live across batches; the call
+    updates them in place."""
+    from .packets import TCP_RCV
+    m, cap = int(m), int(cap)
+    if not 0 <= m <= DEMUX_MAX_ENDPOINTS or not 0 <= cap <= STREAM_MAX_CAP:
+        raise ValueError(f"m must be 0 .. {DEMUX_MAX_ENDPOINTS} and cap 0 .. {STREAM_MAX_CAP}")
+    host = np.zeros(m, dtype=TCP_RCV) if state is None else np.ascontiguousarray(state, dtype=TCP_RCV)
+    if host.shape != (m,):
+        raise ValueError("state must hold m entries of packets.TCP_RCV")
+    st = torch.zeros((max(m, 1), 40), dtype=torch.uint8, device=device)[:m]
+    if m:
+        st.copy_(torch.from_numpy(host.view(np.uint8).reshape(m, 40).copy()))
+    heap = torch.zeros((max(m * cap, 1), 32), dtype=torch.uint8, device=device)[:m * cap]
+    return st, heap
+
+
+def stream_datagrams(records: torch.Tensor, views: torch.Tensor, order: torch.Tensor, first: torch.Tensor, m: int,
+                     receivers, *, ids: torch.Tensor | None = None, acks: bool = False,
+                     status: torch.Tensor | None = None, s_views: torch.Tensor | None = None,
+                     s_offsets: torch.Tensor | None = None, a_records: torch.Tensor | None = None,
+                     a_offsets: torch.Tensor | None = None, n_acks: torch.Tensor | None = None,
+                     work: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None):
+    """TCP segments delivered in order on the device (yu_rx_stream): the reference's
+    receiver.handleRcvdSegment over every TCP connection's queue of a batch. ``records`` and
+    ``views`` are :func:`parse_datagrams`', ``order`` and ``first`` :func:`group_datagrams`',
+    ``receivers`` the ``(st, heap)`` pair of :func:`tcp_receivers`, updated in place; the
+    heap's capacity per endpoint is ``heap.shape[0] // m``.
+
+    Returns ``(status, s_views, s_offsets)``: ``status`` (n uint8) the :data:`SEG_NONE` ..
+    :data:`SEG_UNPROCESSED` verdict per packet; ``s_views`` (shape (N, 2) int64, N = n + m *
+    cap) the delivered payload views in stream order, trimmed, endpoint e's in the slots
+    ``first[e] + e * cap .. first[e+1] + (e + 1) * cap`` from the front, ``(0, 0)`` elsewhere;
+    ``s_offsets`` (N + 1 int64) the exclusive sum of their lengths, so yu_csum_pack_iov(RAW)
+    over the N slots leaves each connection's new in-order bytes contiguous. With ``acks``
+    (which needs ``ids``, shape (m, 16) uint8, the ids :func:`demux_table` was given) it also
+    returns ``(a_records, a_offsets, n_acks)``: one ACK record per connection that owes one
+    (32 zero bytes otherwise), the exclusive sum of 40 per ACK, which
+    ``build_datagrams_iov(zero_views, a_records, a_offsets, dst)`` turns into datagrams, and
+    the number of ACKs the reference would have sent.
+
+    A segment parked out of order keeps a view into the batch it arrived in: keep that
+    memory until it has been delivered. Buffers not given are allocated; with every buffer
+    given the call is capturable in a graph."""
+    _dev_u8(records, "records")
+    dev = records.device
+    if records.dim() != 2 or records.shape[1] != 32:
+        raise ValueError("records must have shape (n, 32)")
+    n = records.shape[0]
+    if records.data_ptr() % 8:
+        raise TypeError("records must be 8-byte aligned")
+    _group_buf(views, (torch.int64,), (n, 2), dev, "views")
+    m = int(m)
+    if not 0 <= m <= DEMUX_MAX_ENDPOINTS:
+        raise ValueError(f"m must be 0 .. {DEMUX_MAX_ENDPOINTS}")
+    _group_buf(order, (torch.int32, torch.uint32), (n,), dev, "order")
+    _group_buf(first, (torch.int64, torch.uint64), (m + 2,), dev, "first")
+    st, heap = receivers
+    _group_buf(st, (torch.uint8,), (m, 40), dev, "receivers[0]")
+    if not isinstance(heap, torch.Tensor) or not heap.is_cuda or heap.device != dev or heap.dtype != torch.uint8 \
+            or heap.dim() != 2 or heap.shape[1] != 32 or not heap.is_contiguous() \
+            or (heap.shape[0] % m if m else heap.shape[0]):
+        raise ValueError("receivers[1] must be the (m * cap, 32) uint8 tensor tcp_receivers returned")
+    cap = heap.shape[0] // m if m else 0
+    if cap > STREAM_MAX_CAP:
+        raise ValueError(f"at most {STREAM_MAX_CAP} heap entries per endpoint")
+    if st.data_ptr() % 8 or heap.data_ptr() % 8:
+        raise TypeError("receivers must be 8-byte aligned")
+    N = n + m * cap
+    if acks:
+        if ids is None:
+            raise ValueError("acks needs ids")
+        _group_buf(ids, (torch.uint8,), (m, 16), dev, "ids")
+    elif a_records is not None or a_offsets is not None or n_acks is not None:
+        raise ValueError("a_records, a_offsets and n_acks go with acks=True")
+
+    def buf(t, shape, dtypes, name, align=8):
+        if t is None:
+            t = torch.empty((max(shape[0], 1),) + tuple(shape[1:]), dtype=dtypes[0], device=dev)[:shape[0]]
+        else:
+            _group_buf(t, dtypes, tuple(shape), dev, name)
+            if t.data_ptr() % align:
+                raise TypeError(f"{name} must be {align}-byte aligned")
+        return t
+
+    status = buf(status, (n,), (torch.uint8,), "status", 1)
+    s_views = buf(s_views, (N, 2), (torch.int64,), "s_views")
+    s_offsets = buf(s_offsets, (N + 1,), (torch.int64, torch.uint64), "s_offsets").view(torch.int64)
+    if acks:
+        a_records = buf(a_records, (m, 32), (torch.uint8,), "a_records")
+        a_offsets = buf(a_offsets, (m + 1,), (torch.int64, torch.uint64), "a_offsets").view(torch.int64)
+        n_acks = buf(n_acks, (m,), (torch.int32, torch.uint32), "n_acks", 4).view(torch.int32)
+    need = stream_workspace_bytes(n, m, cap)
+    if work is None:
+        work = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    else:
+        _dev_u8(work, "work")
+        if work.device != dev:
+            raise TypeError(f"work must be on {dev}")
+        if work.dim() != 1 or work.numel() < need:
+            raise ValueError(f"work must hold stream_workspace_bytes(n, m, cap) = {need} bytes")
+        if work.data_ptr() % 16:
+            raise TypeError("work must be 16-byte aligned")
+    reads = tuple(t for t in (records, views, order, first, ids) if t is not None and t.numel())
+    writes = tuple(t for t in (st, heap, status, s_views, s_offsets, a_records, a_offsets, n_acks, work)
+                   if t is not None and t.numel())
+    for k, t in enumerate(writes):
+        if any(_overlaps(t, s) for s in reads + writes[:k]):
+            raise ValueError("the receivers, the outputs and work must overlap nothing the call reads, nor each other")
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream(dev))
+        for t in reads + writes:
+            t.record_stream(stream)
+    with torch.cuda.device(dev):
+        rc = lib().yu_rx_stream(records.data_ptr() if n else None, views.data_ptr() if n else None, n,
+                                order.data_ptr() if n else None, first.data_ptr(), m,
+                                _ptr(ids) if acks and m else None, st.data_ptr() if m else None,
+                                heap.data_ptr() if m * cap else None, cap, status.data_ptr() if n else None,
+                                s_views.data_ptr() if N else None, s_offsets.data_ptr(),
+                                # with m == 0 the two empty ACK outputs have no address of their own, yet the
+                                # three are given together: a_offsets' stands in, nothing is stored there
+                                (a_records.data_ptr() or a_offsets.data_ptr()) if acks else None, _ptr(a_offsets),
+                                (n_acks.data_ptr() or a_offsets.data_ptr()) if acks else None,
+                                work.data_ptr(), work.numel(), _stream(dev, stream))
+    check(rc, "yu_rx_stream")
+    # the launches read and write these asynchronously: they stay alive with the result, as the
+    # sibling calls keep theirs (group_tables, reply_tables, build_tables)
+    s_offsets.stream_tables = (records, views, order, first, ids, st, heap, work)
+    if acks:
+        return status, s_views, s_offsets, a_records, a_offsets, n_acks
+    return status, s_views, s_offsets
+
+
+def receive_datagrams(data: torch.Tensor, offsets: torch.Tensor, table: torch.Tensor, m: int, receivers, *,
+                      need: int = 0, ids: torch.Tensor | None = None, acks: bool = False,
+                      dst: torch.Tensor | None = None, ack_dst: torch.Tensor | None = None,
+                      stream: torch.cuda.Stream | None = None):
+    """A batch of received IPv4 datagrams turned into each TCP connection's in-order bytes on
+    the device: :func:`parse_datagrams` (with ``verify = need != 0``), yu_rx_demux against
+    ``table, m``, :func:`group_datagrams`, :func:`stream_datagrams` on ``receivers`` and
+    yu_csum_pack_iov(RAW) over the delivered views, asynchronous calls on one stream with no
+    host read between them. With ``acks`` (and ``ids``) the ACK datagrams are built too
+    (:func:`build_datagrams_iov` from a zeroed view table).
+
+    Returns a dict: ``dst`` (the gathered bytes; connection e's new bytes are
+    ``dst[s_offsets[lo] : s_offsets[hi]]`` with ``lo, hi = first[e] + e * cap, first[e+1] + (e +
+    1) * cap``), ``s_offsets``, ``s_views``, ``status``, ``first``, ``order``, ``ep``, ``flags``
+    and, with ``acks``, ``ack_dst``, ``a_offsets``, ``a_records``, ``n_acks``; ``keep`` holds the
+    tensors the asynchronous calls still read (the views point into ``data``): keep the dict
+    until the stream has run.
+
+    ``dst`` is sized by the caller: nothing is read back, so the call cannot check it against
+    ``s_offsets[-1]``. ``data.numel()`` bytes hold everything this batch can deliver; a
+    receiver with ``cap > 0`` may also deliver segments parked by earlier batches, up to
+    ``pend_size`` bytes per connection, and the caller who configured the receivers knows that
+    bound. So ``dst=None`` (a new tensor of ``data.numel()`` bytes) is accepted with ``cap ==
+    0`` only. ``ack_dst`` holds at least 40 bytes per endpoint (the default)."""
+    _dev_u8(data, "data")
+    dev = data.device
+    need = int(need)
+    m = int(m)
+    if not 0 <= m <= DEMUX_MAX_ENDPOINTS:
+        raise ValueError(f"m must be 0 .. {DEMUX_MAX_ENDPOINTS}")
+    # the destinations first: nothing is launched for a call that is refused
+    heap = receivers[1]
+    carried = heap.shape[0] if isinstance(heap, torch.Tensor) and heap.dim() == 2 else 0
+    if dst is None:
+        if carried:
+            raise ValueError("with cap > 0 earlier batches' segments may be delivered too: give dst, sized for "
+                             "data.numel() plus what the receivers may hold")
+        dst = torch.empty(max(data.numel(), 1), dtype=torch.uint8, device=dev)
+    elif _overlaps(_dev_u8(dst, "dst"), data):
+        raise ValueError("dst overlaps data")
+    elif dst.device != dev or dst.numel() < data.numel():
+        raise ValueError("dst must be on the data's device and hold at least data.numel() bytes")
+    if acks:
+        if ack_dst is None:
+            ack_dst = torch.empty(max(40 * m, 1), dtype=torch.uint8, device=dev)
+        elif _dev_u8(ack_dst, "ack_dst").device != dev or ack_dst.numel() < 40 * m:
+            raise ValueError("ack_dst must be on the data's device and hold 40 bytes per endpoint")
+    records, views, flags = parse_datagrams(data, offsets, verify=need != 0, stream=stream)
+    n = records.shape[0]
+    _dev_u8(table, "table")
+    if table.device != dev or table.dim() != 1 or table.numel() != int(lib().yu_demux_table_bytes(m)) \
+            or table.data_ptr() % 16:
+        raise ValueError("table must be the 16-byte aligned tensor demux_table returned for m ids")
+    ep = torch.empty(max(n, 1), dtype=torch.uint32, device=dev)[:n]
+    if stream is not None:
+        table.record_stream(stream)
+        ep.record_stream(stream)
+    with torch.cuda.device(dev):
+        rc = lib().yu_rx_demux(records.data_ptr() if n else None, flags.data_ptr() if n else None, need, n,
+                               table.data_ptr(), table.numel(), m, ep.data_ptr() if n else None, None,
+                               _stream(dev, stream))
+    check(rc, "yu_rx_demux")
+    order, first = group_datagrams(ep, m, stream=stream)
+    res = stream_datagrams(records, views, order, first, m, receivers, ids=ids, acks=acks, stream=stream)
+    status, s_views, s_offsets = res[:3]
+    N = s_views.shape[0]
+    fi = torch.arange(N + 1, dtype=torch.int64, device=dev)
+    sums = torch.empty(max(N, 1), dtype=torch.uint16, device=dev)
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream(dev))  # fi was made on the current stream
+        for t in (fi, sums, dst):
+            t.record_stream(stream)
+    if N:
+        with torch.cuda.device(dev):
+            rc = lib().yu_csum_pack_iov(s_views.data_ptr(), fi.data_ptr(), N, RAW, None, 0, None, dst.data_ptr(),
+                                        s_offsets.data_ptr(), sums.data_ptr(), _stream(dev, stream))
+        check(rc, "yu_csum_pack_iov")
+    out = dict(dst=dst, s_offsets=s_offsets, s_views=s_views, status=status, first=first, order=order, ep=ep,
+               flags=flags, keep=(data, table, records, views, fi, sums))
+    if acks:
+        a_records, a_offsets, n_acks = res[3:]
+        zero_views = torch.zeros((max(m, 1), 2), dtype=torch.int64, device=dev)[:m]
+        if stream is not None:
+            stream.wait_stream(torch.cuda.current_stream(dev))
+            zero_views.record_stream(stream)
+        ack_dst, _, _ = build_datagrams_iov(zero_views, a_records, a_offsets, ack_dst, stream=stream)
+        out.update(ack_dst=ack_dst, a_offsets=a_offsets, a_records=a_records, n_acks=n_acks)
+    return out
+
+
 def split_variant(n: int = 1 << 20) -> str:
     """Name of the kernel :func:`split_datagrams` launches for a batch of n packets."""
     return _wave_variant("rx_split", n)

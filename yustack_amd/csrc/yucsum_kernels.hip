@@ -110,6 +110,10 @@
 //     replies' offsets (yucsum_reply.h).
 //   k_build_iov<U, NT>: yu_tx_build_iov (k_build's plan row): k_build with each
 //     payload behind a view, an empty destination span a skipped packet.
+//   k_stream<RUNS>, k_stream_fin: yu_rx_stream (grid: yu::stream_blocks): a wave
+//     per endpoint runs the TCP receiver over the endpoint's queue, 64 entries per
+//     wave step, in-order runs taken whole; then a lane per element makes the ACK
+//     records and the tail, and k_group_scan_* the offsets (yucsum_stream.h).
 //   All others are grid-stride kernels; the grid is sized per CU and over-subscribed
 //   (see blocks_per_cu in yucsum_plan.cpp), except that k_seg narrows it for
 //   small packets (seg_waves).
@@ -133,6 +137,7 @@
 #include "yucsum_plan.h"
 #include "yucsum_reply.h"
 #include "yucsum_split.h"
+#include "yucsum_stream.h"
 
 namespace {
 
@@ -3810,6 +3815,240 @@ __global__ __launch_bounds__(256) void k_reply(ReplyArgs A) {
 }
 
 // ---------------------------------------------------------------------
+// k_stream: receiver.handleRcvdSegment over every TCP endpoint's queue
+// (yu_rx_stream; yucsum_stream.h has the rule and the walk, yu::stream_endpoint).
+// A wave per endpoint on a grid-stride loop. A wave step is up to 64 queue
+// entries, lane l the l-th: order[j], then the record's two 16-byte halves and
+// the view, and the next step's loads are issued before the current step is
+// processed. The plain run at the front of what is left is found by a prefix sum
+// of the data lengths (__shfl_up) and a ballot; its lanes store their own
+// delivered slot (the view and, into s_offsets[slot], its length: the launches
+// after this one scan that array in place) and their status. Every other entry is
+// broadcast (__shfl) and takes yu::stream_step, the same code and the same
+// addresses on all 64 lanes: the heap is read and written in global memory with
+// ordinary loads and stores, never held in registers. Then the wave stores,
+// lane-strided, its empty slots, the pkt resets of its heap, the words of its state
+// that a walk can change (a lane each; the state byte by lane 0) and its n_acks.
+// The ACK records, which are a function of that state, and the tail of lanes
+// (YU_SEG_NONE for order[first[m] .. n), the empty slots past first[m] + m * cap)
+// are the launch after it, k_stream_fin, a lane per element: kept apart, they do
+// not lengthen what every wave of the walk holds in scalar registers.
+// Store order: the general step's heap and status stores are issued by all 64 lanes
+// to one address with one value, and the epilogue's lane-strided stores (a pkt reset
+// by lane i, a state word by lane k) land on bytes those wrote earlier. This relies on
+// one wave's stores to one address being performed in issue order whichever lane
+// issues them, which holds on gfx9-class hardware (vector memory instructions of a
+// wave reach the cache in order); a target without that order needs a wait between.
+// `first` is clamped to n and made monotone per endpoint,
+// pend_count is clamped to cap, and every packet number, slot and heap index is
+// compared with its bound before the access (in yucsum_stream.h, or here for the
+// lanes' own stores). No LDS, no atomics, no wave waits for another.
+// ---------------------------------------------------------------------
+struct StreamArgs {
+  const uint8_t *recs;    // yu_tx_record, 32 bytes each
+  const uint8_t *views;   // yu_iovec, 16 bytes each
+  const uint32_t *order;
+  const uint64_t *first;  // m + 2
+  uint8_t *st;            // yu_tcp_rcv, 40 bytes each
+  uint8_t *heap;          // yu_tcp_seg, 32 bytes each, m * cap
+  uint8_t *status;
+  uint8_t *s_views;
+  uint64_t *s_offsets;
+  uint32_t *n_acks;       // NULL, or m
+  uint32_t n, m, cap;
+};
+
+// The Wave and Io of yu::stream_endpoint for one endpoint.
+struct StreamWave {
+  const StreamArgs &A;
+  const uint32_t lane;
+  uint32_t e;  // the endpoint: its heap is found from A.heap at each access, one pointer less to hold
+  yu::StreamSeg cur, nxt;
+  uint32_t cur_pl;  // yu::stream_plain_len(cur), once per step: a value in a vector register, not lane masks
+
+  __device__ __forceinline__ uint8_t *ent(uint32_t i) const { return A.heap + 32u * ((uint64_t)e * A.cap + i); }
+
+  __device__ __forceinline__ void load(uint64_t j0, uint32_t cnt) {
+    nxt = yu::StreamSeg{0u, 0u, yu::kDemuxNone, 0u, 0u};
+    if (lane >= cnt) return;
+    const uint32_t pkt = A.order[j0 + lane];
+    nxt.pkt = pkt;
+    if (pkt >= A.n) return;  // an entry without a record: not usable, and its status has no place
+    const u32x4_a8 a = *(const u32x4_a8 *)(A.recs + 32u * (uint64_t)pkt);
+    const u32x4_a8 b = *(const u32x4_a8 *)(A.recs + 32u * (uint64_t)pkt + 16u);
+    const u32x4_a8 v = *(const u32x4_a8 *)(A.views + 16u * (uint64_t)pkt);
+    nxt.seq = a.w, nxt.fdp = yu::stream_fdp(b.y >> 16, b.y >> 24, b.z);
+    nxt.base = (uint64_t)v.x | (uint64_t)v.y << 32, nxt.vlen = v.w ? 0xFFFFFFFFu : v.z;
+  }
+  __device__ __forceinline__ void advance() {
+    cur = nxt;
+    cur_pl = yu::stream_plain_len(cur);
+  }
+
+  __device__ __forceinline__ uint32_t run(const yu::StreamSt &S, const yu::StreamCtx &C, uint32_t k0, uint32_t cnt,
+                                          uint32_t &sum) {
+    const bool in = lane >= k0 && lane < cnt;
+    const uint32_t pl = in ? cur_pl : 0u;
+    uint32_t incl = pl;
+    for (uint32_t o = 1; o < 64u; o <<= 1) {
+      // lane - o's value (ds_bpermute, the index wrapping below lane o) under lane >= o as an
+      // all-ones word that the optimiser cannot see through: as compares (__shfl_up's too)
+      // the six loop-invariant lane masks are hoisted out of the whole walk and each holds a
+      // scalar register pair there, which spills
+      const uint32_t u = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((lane - o) & 63u) << 2), (int)incl);
+      uint32_t keep = (uint32_t)((int32_t)(o - 1u - lane) >> 31);
+      asm volatile("" : "+v"(keep));
+      incl += u & keep;
+    }
+    const uint64_t ballot = __ballot(in && yu::stream_in_run(cur, pl, S, incl - pl));
+    const uint32_t r = yu::stream_run_len(ballot, k0, cnt);
+    sum = 0;
+    if (r == 0u) return 0u;
+    sum = __builtin_amdgcn_readlane(incl, k0 + r - 1u);
+    if (lane >= k0 && lane < k0 + r) {
+      const uint64_t slot = C.slot_lo + S.slots + (lane - k0);
+      if (slot < C.slot_hi) st_slot(slot, cur.base + (yu::seg_doff(cur) - 20u), pl);
+      if (cur.pkt < C.n) st_status(cur.pkt, YU_SEG_CONSUMED);
+    }
+    return r;
+  }
+  __device__ __forceinline__ void fill(uint32_t k0, uint32_t cnt, uint32_t v) {
+    if (lane >= k0 && lane < cnt && cur.pkt < A.n) st_status(cur.pkt, v);
+  }
+  // Lane k's entry for every lane: k is wave-uniform, so these are v_readlane and the
+  // general step's values and branches are scalar.
+  __device__ __forceinline__ yu::StreamSeg seg(uint32_t k) const {
+    yu::StreamSeg s;
+    const uint32_t b0 = __builtin_amdgcn_readlane((uint32_t)cur.base, k);
+    const uint32_t b1 = __builtin_amdgcn_readlane((uint32_t)(cur.base >> 32), k);
+    s.base = (uint64_t)b0 | (uint64_t)b1 << 32;
+    s.vlen = __builtin_amdgcn_readlane(cur.vlen, k), s.pkt = __builtin_amdgcn_readlane(cur.pkt, k);
+    s.seq = __builtin_amdgcn_readlane(cur.seq, k), s.fdp = __builtin_amdgcn_readlane(cur.fdp, k);
+    return s;
+  }
+
+  __device__ __forceinline__ yu::StreamEnt ld_heap(uint32_t i) const {
+    const u32x4_a8 a = *(const u32x4_a8 *)ent(i);
+    const u32x4_a8 b = *(const u32x4_a8 *)(ent(i) + 16u);
+    return yu::StreamEnt{(uint64_t)a.x | (uint64_t)a.y << 32, a.w ? 0xFFFFFFFFu : a.z, b.x, b.y, b.z & 0xFFu};
+  }
+  __device__ __forceinline__ uint32_t ld_heap_seq(uint32_t i) const {
+    return *(const uint32_t *)(ent(i) + 16u);
+  }
+  __device__ __forceinline__ void mv_heap(uint32_t to, uint32_t from) const {
+    const u32x4_a8 a = *(const u32x4_a8 *)ent(from);
+    const u32x4_a8 b = *(const u32x4_a8 *)(ent(from) + 16u);
+    *(u32x4_a8 *)ent(to) = a;
+    *(u32x4_a8 *)(ent(to) + 16u) = b;
+  }
+  __device__ __forceinline__ void st_heap(uint32_t i, const yu::StreamEnt &x) const {
+    u32x4_a8 a, b;
+    a.x = (uint32_t)x.base, a.y = (uint32_t)(x.base >> 32), a.z = x.len, a.w = 0u;
+    b.x = x.seq, b.y = x.pkt, b.z = x.flags & 0xFFu, b.w = 0u;
+    *(u32x4_a8 *)ent(i) = a;
+    *(u32x4_a8 *)(ent(i) + 16u) = b;
+  }
+  __device__ __forceinline__ void st_status(uint32_t pkt, uint32_t v) const { A.status[pkt] = (uint8_t)v; }
+  __device__ __forceinline__ void st_slot(uint64_t slot, uint64_t base, uint32_t len) const {
+    u32x4_a8 v;
+    v.x = (uint32_t)base, v.y = (uint32_t)(base >> 32), v.z = len, v.w = 0u;
+    *(u32x4_a8 *)(A.s_views + 16u * slot) = v;
+    A.s_offsets[slot] = len;
+  }
+};
+
+template <bool RUNS>
+__global__ __launch_bounds__(256) void k_stream(StreamArgs A) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = (uint32_t)grid_wave(0u);
+  const uint32_t nwave = gridDim.x * (blockDim.x >> 6);
+  StreamWave W = {A, lane, 0u, {}, {}, 0u};
+  for (uint32_t e = wave; e < A.m; e += nwave) {
+    const uint64_t f0 = A.first[e], f1 = A.first[e + 1u];
+    const uint32_t lo = f0 < A.n ? (uint32_t)f0 : A.n;
+    const uint32_t hi = f1 < lo ? lo : (f1 < A.n ? (uint32_t)f1 : A.n);
+    const yu::StreamCtx C = {lo + (uint64_t)e * A.cap, hi + ((uint64_t)e + 1u) * A.cap, A.n, A.cap};
+    yu::StreamSt S = {};
+    bool touched = false;
+    uint32_t *const st = (uint32_t *)(A.st + 4u * yu::kStreamStWords * (uint64_t)e);
+    if (hi > lo) {
+      uint32_t w[10];
+#pragma unroll
+      for (uint32_t k = 0; k < 10u; ++k) w[k] = st[k];
+      yu::stream_unpack(S, w);
+      if (S.pend_count > A.cap) S.pend_count = A.cap;
+      touched = S.state == yu::kStreamOpen || S.state == yu::kStreamClosed;
+      W.e = e;
+      yu::stream_endpoint(W, C, S, lo, hi - lo, RUNS);
+    }
+    const uint64_t room = C.slot_hi - C.slot_lo;
+    for (uint64_t slot = C.slot_lo + (S.slots < room ? S.slots : room) + lane; slot < C.slot_hi; slot += 64u)
+      W.st_slot(slot, 0u, 0u);
+    uint32_t ln = lane;  // the lane number again, opaque: the masks below are made here, not held from the start
+    asm volatile("" : "+v"(ln));
+    if (touched) {
+      for (uint32_t i = ln; i < S.pend_count; i += 64u) *(uint32_t *)(W.ent(i) + 20u) = yu::kDemuxNone;
+      if (yu::stream_word_changes(ln)) st[ln] = yu::stream_pack_word(S, ln);
+      if (ln == 0u) ((uint8_t *)st)[yu::kStreamStateByte] = (uint8_t)S.state;
+    }
+    if (A.n_acks && ln == 0u) A.n_acks[e] = S.n_acks;
+  }
+}
+
+// yu_rx_stream's second launch, a lane per element: the ACK record of every endpoint
+// from the state k_stream left and its n_acks (32 zero bytes and an offset of 0
+// where that is 0; 40 left in a_offsets[e] otherwise, scanned in place afterwards),
+// YU_SEG_NONE for the packets without an endpoint, order[first[m] .. n), and the
+// empty slots past first[m] + m * cap, their lengths into s_offsets.
+struct StreamFinArgs {
+  const uint32_t *order;
+  const uint64_t *first;
+  const uint32_t *ids;    // yu_endpoint_id, four dwords each; read only for an endpoint that sends an ACK
+  const uint32_t *st;
+  const uint32_t *n_acks;
+  uint8_t *a_recs;        // NULL: no ACK outputs
+  uint64_t *a_offsets;
+  uint8_t *status;
+  uint8_t *s_views;
+  uint64_t *s_offsets;
+  uint32_t n, m, cap;
+};
+
+__global__ __launch_bounds__(256) void k_stream_fin(StreamFinArgs A) {
+  const uint64_t tid = (uint64_t)blockIdx.x * 256u + threadIdx.x, nthreads = (uint64_t)gridDim.x * 256u;
+  if (A.a_recs)
+    for (uint64_t e = tid; e < A.m; e += nthreads) {
+      const uint32_t na = A.n_acks[e];
+      uint32_t w[10] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}, id0 = 0, id1 = 0, id2 = 0;
+      if (na) {
+#pragma unroll
+        for (uint32_t k = 0; k < 10u; ++k) w[k] = A.st[yu::kStreamStWords * e + k];
+        id0 = A.ids[4u * e], id1 = A.ids[4u * e + 1u], id2 = A.ids[4u * e + 2u];
+      }
+      u32x4_a8 r0, r1;
+      r0.x = yu::stream_ack_word(w, na, id0, id1, id2, 0u), r0.y = yu::stream_ack_word(w, na, id0, id1, id2, 1u);
+      r0.z = yu::stream_ack_word(w, na, id0, id1, id2, 2u), r0.w = yu::stream_ack_word(w, na, id0, id1, id2, 3u);
+      r1.x = yu::stream_ack_word(w, na, id0, id1, id2, 4u), r1.y = yu::stream_ack_word(w, na, id0, id1, id2, 5u);
+      r1.z = yu::stream_ack_word(w, na, id0, id1, id2, 6u), r1.w = yu::stream_ack_word(w, na, id0, id1, id2, 7u);
+      *(u32x4_a8 *)(A.a_recs + 32u * e) = r0;
+      *(u32x4_a8 *)(A.a_recs + 32u * e + 16u) = r1;
+      A.a_offsets[e] = na ? (uint64_t)yu::kStreamAckBytes : 0u;
+    }
+  uint64_t d = A.first[A.m];
+  if (d > A.n) d = A.n;
+  for (uint64_t j = d + tid; j < A.n; j += nthreads) {
+    const uint32_t pkt = A.order[j];
+    if (pkt < A.n) A.status[pkt] = (uint8_t)YU_SEG_NONE;
+  }
+  const uint64_t N = A.n + (uint64_t)A.m * A.cap;
+  const u32x4_a8 zero = {0u, 0u, 0u, 0u};
+  for (uint64_t slot = d + (uint64_t)A.m * A.cap + tid; slot < N; slot += nthreads) {
+    *(u32x4_a8 *)(A.s_views + 16u * slot) = zero;
+    A.s_offsets[slot] = 0u;
+  }
+}
+
+// ---------------------------------------------------------------------
 // The kernels of yu_rx_group (yucsum_group.h has the arithmetic and the
 // picture): the packet numbers grouped by endpoint, stable, as a
 // least-significant-digit radix partition of (key, packet number), key =
@@ -4559,6 +4798,73 @@ int rx_reply(const yu_tx_record *recs, const uint16_t *flags, uint16_t need, con
   return hip_status(hipGetLastError());
 }
 
+// yu_rx_stream: its arguments, then k_stream on yu::stream_blocks' grid, which
+// leaves every slot's length in s_offsets[slot] and 40 or 0 in a_offsets[e], and
+// the scan of yu_rx_group over both in place, one after the other, their tile
+// sums in the caller's workspace. At n == 0 every output is zero and is stored so.
+const char *stream_name(uint64_t n, uint64_t m, uint32_t cap) {
+  if (yu::stream_workspace_bytes(n, m, cap) == 0u) return "none";
+  return yu::env_knobs().stream_walk ? "k_stream<walk>" : "k_stream";
+}
+
+void stream_zero(void *p, uint64_t dwords, hipStream_t stream) {
+  if (!p || !dwords) return;
+  const uint64_t blocks = (dwords + 255u) / 256u;
+  hipLaunchKernelGGL(k_group_zero, dim3((uint32_t)(blocks < 65536u ? blocks : 65536u)), dim3(256), 0, stream,
+                     (uint32_t *)p, dwords, (uint32_t *)nullptr, (uint64_t)0);
+}
+
+int rx_stream(const yu_tx_record *recs, const yu_iovec *views, uint64_t n, const uint32_t *order,
+              const uint64_t *first, uint64_t m, const yu_endpoint_id *ids, yu_tcp_rcv *st, yu_tcp_seg *heap,
+              uint32_t cap, uint8_t *status, yu_iovec *s_views, uint64_t *s_offsets, yu_tx_record *a_recs,
+              uint64_t *a_offsets, uint32_t *n_acks, void *work, uint64_t work_bytes, void *stream_) {
+  if (!aligned(recs, 8) || !aligned(views, 8) || !aligned(first, 8) || !aligned(st, 8) || !aligned(heap, 8) ||
+      !aligned(s_views, 8) || !aligned(s_offsets, 8) || !aligned(a_recs, 8) || !aligned(a_offsets, 8) ||
+      !aligned(work, 16))
+    return YU_EINVAL;                                                        // EINVAL:offsets
+  if (!aligned(order, 4) || !aligned(ids, 4) || !aligned(n_acks, 4)) return YU_EINVAL;  // EINVAL:side-align
+  if (m > yu::kDemuxMax || n >= (1ull << 32) || cap > yu::kStreamMaxCap) return YU_EINVAL;  // EINVAL:data
+  if (m > 0 && !st) return YU_EINVAL;                                        // EINVAL:data
+  if ((a_recs != nullptr) != (a_offsets != nullptr) || (a_recs != nullptr) != (n_acks != nullptr))
+    return YU_EINVAL;                                                        // EINVAL:data
+  const uint64_t N = n + m * cap;
+  if (!s_offsets && (m > 0 || n > 0)) return YU_EINVAL;                      // EINVAL:out
+  if (!s_views && N > 0) return YU_EINVAL;                                   // EINVAL:out
+  hipStream_t stream = (hipStream_t)stream_;
+  int dev = 0;
+  if (n == 0) {  // the empty tables are stored; no state, no heap entry and no input is touched
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return hip_status(e);
+    stream_zero(s_views, 4u * N, stream);
+    stream_zero(s_offsets, 2u * (N + 1u), stream);
+    stream_zero(a_recs, 8u * m, stream);
+    stream_zero(a_offsets, 2u * (m + 1u), stream);
+    stream_zero(n_acks, m, stream);
+    return hip_status(hipGetLastError());
+  }
+  if (!status) return YU_EINVAL;                                             // EINVAL:out
+  if (!recs || !views || !order || !first || !work || work_bytes < yu::stream_workspace_bytes(n, m, cap))
+    return YU_EINVAL;                                                        // EINVAL:data
+  if ((!heap && m * cap > 0) || (!ids && a_recs && m > 0)) return YU_EINVAL;  // EINVAL:data
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return hip_status(e);
+  const yu::Knobs &k = yu::env_knobs();
+  const StreamArgs a = {(const uint8_t *)recs, (const uint8_t *)views, order, first, (uint8_t *)st,
+                        (uint8_t *)heap, status, (uint8_t *)s_views, s_offsets, n_acks,
+                        (uint32_t)n, (uint32_t)m, cap};
+  const uint32_t cus = (uint32_t)cu_count(dev);
+  if (m)
+    hipLaunchKernelGGL(k.stream_walk ? k_stream<false> : k_stream<true>,
+                       dim3(yu::stream_blocks(0u, m, cus, k.blocks_per_cu)), dim3(256), 0, stream, a);
+  const StreamFinArgs f = {order, first, (const uint32_t *)ids, (const uint32_t *)st, n_acks, (uint8_t *)a_recs,
+                           a_offsets, status, (uint8_t *)s_views, s_offsets, (uint32_t)n, (uint32_t)m, cap};
+  hipLaunchKernelGGL(k_stream_fin, dim3(yu::stream_blocks(n, (m + 63u) / 64u, cus, k.blocks_per_cu)), dim3(256), 0,
+                     stream, f);
+  group_scan<uint64_t, uint64_t>(s_offsets, N, s_offsets, N + 1u, (uint64_t *)work, stream);
+  if (a_recs) group_scan<uint64_t, uint64_t>(a_offsets, m, a_offsets, m + 1u, (uint64_t *)work, stream);
+  return hip_status(hipGetLastError());
+}
+
 // Completion signal for the host path's direct mode (yucsum_internal.h):
 // stored after the work before it on the stream, with system-scope release,
 // into coherent pinned host memory.
@@ -4755,6 +5061,20 @@ int yu_rx_reply(const yu_tx_record *recs, const uint16_t *flags, uint16_t need, 
 const char *yu_rx_reply_variant_n(uint64_t n) {
   return yu::plan_reply(n, 256, yu::env_knobs()).name;
 }
+
+uint64_t yu_rx_stream_workspace_bytes(uint64_t n, uint64_t m, uint32_t cap) {
+  return yu::stream_workspace_bytes(n, m, cap);
+}
+
+int yu_rx_stream(const yu_tx_record *recs, const yu_iovec *views, uint64_t n, const uint32_t *order,
+                 const uint64_t *first, uint64_t m, const yu_endpoint_id *ids, yu_tcp_rcv *st, yu_tcp_seg *heap,
+                 uint32_t cap, uint8_t *status, yu_iovec *s_views, uint64_t *s_offsets, yu_tx_record *a_recs,
+                 uint64_t *a_offsets, uint32_t *n_acks, void *work, uint64_t work_bytes, void *stream) {
+  return rx_stream(recs, views, n, order, first, m, ids, st, heap, cap, status, s_views, s_offsets, a_recs,
+                   a_offsets, n_acks, work, work_bytes, stream);
+}
+
+const char *yu_rx_stream_variant_n(uint64_t n, uint64_t m, uint32_t cap) { return stream_name(n, m, cap); }
 
 const char *yu_uniform_variant(uint64_t stride, uint32_t len, int mode,
                                uint64_t data_align16) {

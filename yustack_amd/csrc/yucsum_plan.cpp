@@ -234,6 +234,8 @@ Knobs read_knobs(const char *(*get)(const char *name)) {
   // share at most one line between neighbouring blocks, and the Infinity Cache
   // already absorbs its second fetch — and -1..3 % on configs 2/3, so it is off.
   k.xcd = knob_int(get("YU_XCD"), 0, 1, 0) != 0;
+  // YU_STREAM=walk: k_stream without its plain runs, one general step per queue entry.
+  if (const char *f = get("YU_STREAM")) k.stream_walk = strcmp(f, "walk") == 0;
   return k;
 }
 

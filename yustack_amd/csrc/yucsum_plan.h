@@ -149,6 +149,7 @@ struct Knobs {
   uint16_t blocks_per_cu = 0;    // YU_BLOCKS_PER_CU: grid size in 256-thread blocks per CU; 0 = per kernel
   uint8_t seg_small_blocks = 3;  // YU_SEG_SMALL_BLOCKS
   bool xcd = false;              // YU_XCD
+  bool stream_walk = false;      // YU_STREAM=walk: k_stream takes the general step for every entry (A/B, equality test)
 };
 // Knobs from their text form: `get` returns a knob's value, or NULL when unset.
 Knobs read_knobs(const char *(*get)(const char *name));

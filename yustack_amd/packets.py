@@ -187,6 +187,33 @@ def endpoint_ids(m: int, *, local_addr=0, remote_addr=0, local_port=0, remote_po
     return ids
 
 
+# struct yu_tcp_rcv and struct yu_tcp_seg (include/yucsum.h): the per-connection receiver
+# state and one pending segment of batch.stream_datagrams.
+TCP_RCV = np.dtype([("rcv_nxt", np.uint32), ("rcv_acc", np.uint32), ("pend_used", np.uint32),
+                    ("pend_size", np.uint32), ("buf_size", np.uint32), ("buf_used", np.uint32),
+                    ("snd_nxt", np.uint32), ("max_sent_ack", np.uint32), ("pend_count", np.uint32),
+                    ("wnd_scale", np.uint8), ("state", np.uint8), ("reserved", np.uint16)])
+TCP_SEG = np.dtype([("base", np.uint64), ("len", np.uint64), ("seq", np.uint32), ("pkt", np.uint32),
+                    ("flags", np.uint8), ("reserved", np.uint8, (7,))])
+assert TCP_RCV.itemsize == 40 and TCP_SEG.itemsize == 32
+
+
+def tcp_rcv(m: int, *, rcv_nxt=0, wnd=65535, snd_nxt=0, wnd_scale=0, state=1) -> np.ndarray:
+    """m receivers of :data:`TCP_RCV` as newReceiver leaves them (transport/tcp/rcv.go:32-40):
+    ``rcv_acc = rcv_nxt + wnd``, ``pend_size = buf_size = wnd``, nothing pending, nothing
+    buffered, ``max_sent_ack = rcv_nxt``; each argument an array of m values or a scalar.
+    ``state`` 0 marks an endpoint the stream call does not serve (UDP, a listener)."""
+    st = np.zeros(m, dtype=TCP_RCV)
+    nxt = np.broadcast_to(np.asarray(rcv_nxt, dtype=np.uint32), (m,))
+    w = np.broadcast_to(np.asarray(wnd, dtype=np.uint32), (m,))
+    st["rcv_nxt"], st["rcv_acc"], st["max_sent_ack"] = nxt, nxt + w, nxt
+    st["pend_size"], st["buf_size"] = w, w
+    st["snd_nxt"] = np.broadcast_to(np.asarray(snd_nxt, dtype=np.uint32), (m,))
+    st["wnd_scale"] = np.broadcast_to(np.asarray(wnd_scale, dtype=np.uint8), (m,))
+    st["state"] = np.broadcast_to(np.asarray(state, dtype=np.uint8), (m,))
+    return st
+
+
 # YU_RX_SPLIT (include/yucsum.h): the bit batch.split_datagrams adds to VERIFY_RX's flags
 # when a packet's record, pay_len and payload are defined.
 RX_SPLIT = 16
